@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- rollout-steps/s of the DPhysics hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs and nothing else: it sets up the workload, warms up, chooses the launch mode,
+times the K steps and prints the result line (the contract's keys, `config`; no detail file).  `--full` adds everything else
+this script measures -- `roofline` with its per-kernel HIP-event figures, `comm_ms`, `forward_only`, the sweeps, the side
+workloads, `cpu_baseline` and the detail file -- as described below.  `--dump-outputs DIR` writes what the timed path computed
+in its LAST timed step, as a caller of that path receives it, to DIR/<name>.npy (float32 / float64, at most 64 MB in all; see
+`dump_outputs`): the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1: one rank per GPU over RCCL.  Either the caller launches the ranks (`python -m torch.distributed.run --nproc-per-node N
 ... bench.py --gpus N`, RANK / LOCAL_RANK / WORLD_SIZE in the env) or, when WORLD_SIZE is absent, bench.py re-executes itself
@@ -14,7 +21,7 @@ max over ranks), inputs resident in HBM, outputs allocated inside the timed regi
 the step is replayed as a hipGraph, owned by the captured graph.  Launch mode (`config.launch`): after the warm-up the step is
 timed both ways on the host at hand -- launched call by call, and captured once and replayed as ONE hipGraph launch per step
 (same kernels, same work) -- and the timed region runs in the faster mode; MF_BENCH_NO_GRAPH=1 keeps it launch by launch.
-Kernel durations for `roofline` come from HIP events around the C-ABI launches of every 32nd timed step and of four steps run right after the region (those steps run
+Kernel durations for `roofline` (--full) come from HIP events around the C-ABI launches of every 32nd timed step and of four steps run right after the region (those steps run
 launch by launch in either mode).
 Rollouts are independent: ranks shard the batch with no data-path collective (weak scaling: B rollouts per GPU); the
 backward all-reduces the gradient of what the ranks SHARE -- one terrain / friction map pair, the same on every rank
@@ -28,14 +35,14 @@ Workloads (`--workload`; the default, c3, is BASELINE configs[2], the shape nort
   c4   BASELINE configs[3]   TerrainEncoder (4 cams 3x256x512 -> 256x256 BEV) + 1024 rollouts, end-to-end train step
   c5   BASELINE configs[4]   8192 rollouts in total + encoder, sharded over the ranks (STRONG scaling: 8192 / N per GPU)
 
-OUTPUT.  The LAST stdout line (rank 0) is ONE compact JSON object, < 4 KB (`compact_line`): the contract's keys, `config`, `roofline`
-(bound, achieved, peak, unit, frac, traffic, frac_traffic, frac_model, kernel, kernel_ms, ...), `cpu_baseline` (value, unit, cores,
-kind, sample), `forward_only` and one ms-per-step number per side workload.  Everything else -- per-kernel tables, the batch sweep,
-side workloads, CPU legs, kernel-instance strings -- goes to the DETAIL file (`--detail`, default bench_detail.json next to this
-script, copied to gpurun_out/ when that directory exists); the line names it under `detail`.  (Round 5 printed all of it as one
-28.8 KB line, which the driver could not parse: tests/test_bench_line_cpu.py holds the line to its size now.)
+OUTPUT.  The LAST stdout line (rank 0) is ONE compact JSON object, < 4 KB (`compact_line`): the contract's keys, `config` and, with
+--full, `roofline` (bound, achieved, peak, unit, frac, traffic, frac_traffic, frac_model, kernel, kernel_ms, ...), `cpu_baseline`
+(value, unit, cores, kind, sample), `forward_only` and one ms-per-step number per side workload.  Everything else -- per-kernel
+tables, the batch sweep, side workloads, CPU legs, kernel-instance strings -- goes to the DETAIL file of a --full run (`--detail`,
+default bench_detail.json next to this script); the line names it under `detail`.  (Round 5 printed all of it as one 28.8 KB
+line, too long to be parsed: tests/test_bench_line_cpu.py holds the line to its size now.)
 
-The detail record carries, besides the contract's keys:
+The detail record (--full) carries, besides the contract's keys:
   roofline      dominant hand-written kernel of the headline step -- algorithmic bytes per launch (80 + 56 N
                 bytes per rollout-step forward, 160 + 120 N backward) / its average launch duration, measured live with HIP
                 events on the launch stream, against the 8 TB/s HBM peak -- plus `per_kernel` (forward AND backward
@@ -45,7 +52,7 @@ The detail record carries, besides the contract's keys:
   forward_only  the c3f workload, same accounting (top level: both the forward-only and the forward+backward rate count)
   cpu_baseline  the CPU oracle (oracle/dphysics_oracle.py, a torch-CPU port of the reference algorithm) timed on this box's
                 host cores on bounded samples: forward (no_grad), the autograd forward+backward of config 3, and config 1.
-  other_workloads  (default run) short runs of c1, c2, c4 and `shoot` (trajectory shooting of 16384 sampled control
+  other_workloads  (--full) short runs of c1, c2, c4 and `shoot` (trajectory shooting of 16384 sampled control
                 sequences through the kernel's path-cost mode); N > 1: `strong_c3` (8192 rollouts in total) and c5.
 """
 import argparse
@@ -356,8 +363,9 @@ class Runner:
             self.dist_world = dist.get_world_size()        # what the collective library itself sees
         # PMC-measured HBM bytes per launch (tools/collect_profiles.sh): valid for the library build they were measured on -- the file
         # carries that build's sha256, and a different library gets `traffic: null` with the reason instead of a stale figure
+        # (--full only: `roofline` is the one reader)
         traffic_file = os.path.join(REPO, 'profiles', 'hbm_traffic.json')
-        self.traffic = json.load(open(traffic_file)) if os.path.exists(traffic_file) else {}
+        self.traffic = json.load(open(traffic_file)) if args.full and os.path.exists(traffic_file) else {}
         self.traffic_stale = None
         want = self.traffic.get('_library_sha256')
         if self.traffic:
@@ -394,7 +402,10 @@ class Runner:
         torch.cuda.synchronize(self.dev)
         return self.max_over_ranks((time.perf_counter() - t) / n * 1e3)
 
-    def run(self, name, steps, warmup, batch=0, events_after=False):
+    def run(self, name, steps, warmup, batch=0, events_after=False, measure=True, keep_outputs=False):
+        """Time `steps` steps of workload `name` after `warmup` (and the launch-mode calibration).  measure=False (a plain run's
+        headline): a bare timed region -- no HIP events in it or after it, no exchange timing, no `roofline`.  keep_outputs: the
+        record carries, under `outputs`, host copies of what the LAST timed step handed its caller."""
         from monoforce_amd import _timing
         args, dev, world, rank = self.args, self.dev, self.world, self.rank
         wl = dict(WORKLOADS[name])
@@ -453,7 +464,7 @@ class Runner:
 
         use_graph = not os.environ.get('MF_BENCH_NO_GRAPH')
         mode = {'graph': False}
-        fwd_graph = None
+        fwd_graph = fwd_out = None
 
         def forward_eager():
             with torch.no_grad():
@@ -472,6 +483,7 @@ class Runner:
             if eager:
                 return forward_eager()
             fwd_graph.replay()
+            return fwd_out      # (the graph's own output tensors, rewritten by every replay)
 
         for _ in range(warmup):
             step()
@@ -491,7 +503,7 @@ class Runner:
                 from monoforce_amd.capture import capture
                 fwd_graph = torch.cuda.CUDAGraph()
                 with capture(fwd_graph, stream=side, capture_error_mode='thread_local'):
-                    forward_eager()
+                    fwd_out = forward_eager()
 
             def timed(graph, n=(2 if (self.dist_on and self.backend != 'nccl') else 8) if wl.get('encoder') else 32):      # (gloo test rig: every encoder step carries a host-side exchange)
                 mode['graph'] = graph
@@ -516,14 +528,34 @@ class Runner:
         # (`events_after`, the side workloads of the default line -- a handful of steps each: a step bracketed with events runs launch by
         #  launch, and one such step among five replays of a 16 ms graph IS the average on a host that is slow at launching -- c4 read
         #  20.1 ms where its replays take 16.4.  Their timed region is K replays; the kernel durations come from sampled steps after it.)
-        if not events_after:
+        if measure and not events_after:
             _timing.start(every=EVENT_EVERY)
         t0 = time.perf_counter()
         for _ in range(steps):
             _timing.next_step()
-            step()
+            last = step()
         self.barrier()
         elapsed = time.perf_counter() - t0
+        outputs = None
+        if keep_outputs:      # (before anything else runs a step: the encoder's steps update its weights)
+            if wl.get('encoder'):
+                loss, (l_geom, l_terr, l_phys) = last
+                named = {'loss': loss, 'loss_geom': l_geom, 'loss_terrain': l_terr, 'loss_phys': l_phys}
+            elif wl['backward']:      # the loss, and the gradients the step leaves in .grad of the terrain and friction leaves
+                named = {'loss': last, 'grad_z': zleaf.grad, 'grad_mu': mleaf.grad}
+            else:
+                (Xs, Xds, Rs, Om), (Fs, Ff) = last
+                named = {'Xs': Xs, 'Xds': Xds, 'Rs': Rs, 'Om': Om, 'Fs': Fs, 'Ff': Ff}
+            outputs = {k: (v.detach() if v.dtype in (torch.float32, torch.float64) else v.detach().double()).cpu().numpy()
+                       for k, v in named.items() if v is not None}
+        mode_text = 'encoder train step (fwd+bwd+Adam)' if wl.get('encoder') else 'forward+backward' if wl['backward'] else 'forward'
+        integ = 'odeint-euler (reference default)' if args.integrator == 1 else 'dynamics()'
+        H = int(round(12.8 / res))
+        if not measure:
+            elapsed_min, elapsed = self.max_over_ranks(elapsed, 'MIN'), self.max_over_ranks(elapsed)
+            del dp
+            return self._record(name, wl, steps, warmup, elapsed, elapsed_min, strong, B, B_total, T, N, H, res, integ, mode_text, launch, {},
+                                outputs), (N, T)
         # more samples of the kernel durations from steps run right after the region (untimed; a bracketed step runs launch by launch,
         # which is why the region itself carries few of them: at K = 20 every 8th step was 3 of 20 steps at 0.45-0.58 instead of 0.385 ms)
         if events_after:
@@ -584,9 +616,6 @@ class Runner:
                 f'SURVEY 8d: 160 + 120 N = {bwd_bytes_per_rollout_step(N)} B per rollout-step (of which 72 + 24 N are upstream-gradient rows a fused '
                 f'physics loss never reads: the kernel forms dL/dXs itself)')
         achieved = per_kernel[dom]['GB/s']
-        mode = 'encoder train step (fwd+bwd+Adam)' if wl.get('encoder') else 'forward+backward' if wl['backward'] else 'forward'
-        integ = 'odeint-euler (reference default)' if args.integrator == 1 else 'dynamics()'
-        H = int(round(12.8 / res))
         traffic = self.traffic.get(name if not batch else f'{name}_B{B}', {}).get(dom)
         # the per-step record small default-integrator launches keep in the forward for the backward (MfRolloutFwdBufs.rec): real
         # bytes on top of the algorithmic ones -- a recompute-for-storage trade, reported so that `traffic` reads right
@@ -598,14 +627,9 @@ class Runner:
                                    math_mode=_lib.MF_MATH_FAST, force_stride=max(N, 4), map_shared=1, layout=_lib.MF_LAYOUT_TIME_MAJOR)
             rec_bytes = int(_lib.lib().mf_rollout_record_bytes(C.byref(d)))
         out = {
-            'value': B_total * T * steps / elapsed, 'steps': steps, 'warmup': warmup, 'ms_per_step': elapsed / steps * 1e3,
-            'ms_per_step_ranks': {'min': elapsed_min / steps * 1e3, 'max': elapsed / steps * 1e3}, 'comm_ms': comm_ms,
-            'scaling': 'strong' if strong else 'weak',
-            'config': {'workload': f'{name}: B={B}/GPU x T={T} x N={N} contact points, {H}x{H} grid (res {res} m), one shared '
-                                   f'terrain+friction map (the same on every rank), integrator={integ}, {mode}; {wl["desc"]}',
-                       'rollouts_per_gpu': B, 'rollouts_total': B_total, 'horizon': T, 'contact_points': N, 'grid': [H, H],
-                       'parallelism': f'rollout-sharded x{world}',
-                       'launch': {**(launch or {'mode': 'launch by launch'}), 'kernels': kernels_run}},
+            **self._record(name, wl, steps, warmup, elapsed, elapsed_min, strong, B, B_total, T, N, H, res, integ, mode_text, launch,
+                           kernels_run, outputs),
+            'comm_ms': comm_ms,
             'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
                          'traffic': traffic,
                          # the PMC-measured HBM bytes per launch over the kernel's measured duration: what the memory system really sustained
@@ -629,6 +653,23 @@ class Runner:
         }
         del dp
         return out, (N, T)
+
+    def _record(self, name, wl, steps, warmup, elapsed, elapsed_min, strong, B, B_total, T, N, H, res, integ, mode, launch, kernels_run,
+                outputs):
+        """The headline part of a workload's record: rate, ms per step, scaling, config (`elapsed`: the max over the ranks)."""
+        out = {
+            'value': B_total * T * steps / elapsed, 'steps': steps, 'warmup': warmup, 'ms_per_step': elapsed / steps * 1e3,
+            'ms_per_step_ranks': {'min': elapsed_min / steps * 1e3, 'max': elapsed / steps * 1e3},
+            'comm_ms': None, 'scaling': 'strong' if strong else 'weak',
+            'config': {'workload': f'{name}: B={B}/GPU x T={T} x N={N} contact points, {H}x{H} grid (res {res} m), one shared '
+                                   f'terrain+friction map (the same on every rank), integrator={integ}, {mode}; {wl["desc"]}',
+                       'rollouts_per_gpu': B, 'rollouts_total': B_total, 'horizon': T, 'contact_points': N, 'grid': [H, H],
+                       'parallelism': f'rollout-sharded x{self.world}',
+                       'launch': {**(launch or {'mode': 'launch by launch'}), 'kernels': kernels_run}},
+        }
+        if outputs is not None:
+            out['outputs'] = outputs
+        return out
 
     def batch_sweep(self, N, T, batches=(256, 1024, 4096, 8192, 16384, 32768, 65536), private_batches=(256, 1024)):
         """Forward and backward rollout kernels over the batch (256 ... 65 536 rollouts; kernel time from HIP events; not part
@@ -878,9 +919,9 @@ def _r(v, sig=6):
 
 
 def compact_line(out, detail_file=None):
-    """The ONE line the driver parses: the contract's keys + `roofline` + `cpu_baseline`, every value a number or a short string.
-    Sweeps, side workloads, per-kernel tables, kernel-name strings and CPU legs live in the detail file (`detail`)."""
-    cfg, roof = out['config'], out['roofline']
+    """The ONE result line, the last on stdout: the contract's keys + `roofline` + `cpu_baseline` (the last two: --full), every value a
+    number or a short string.  Sweeps, side workloads, per-kernel tables, kernel-name strings and CPU legs live in the detail file (`detail`)."""
+    cfg, roof = out['config'], out.get('roofline') or {}
     c = {k: _r(out.get(k)) for k in ('metric', 'value', 'unit', 'n_gpus', 'world_size', 'backend', 'steps', 'warmup', 'ms_per_step')}
     if out.get('ms_per_step_ranks'):
         c['ms_per_step_ranks'] = {k: _r(v) for k, v in out['ms_per_step_ranks'].items()}
@@ -898,6 +939,8 @@ def compact_line(out, detail_file=None):
         c['roofline']['regime'] = _short(roof['regime'], 160)
     pk = roof.get('per_kernel') or {}
     c['roofline']['per_kernel_ms'] = {k: _r(v['ms'], 4) for k, v in pk.items() if isinstance(v, dict) and 'ms' in v and not k.endswith('_all_outputs')}
+    if 'roofline' not in out:      # a plain run: no roofline measured
+        del c['roofline']
     if out.get('forward_only'):
         f = out['forward_only']
         c['forward_only'] = {'value': _r(f['value']), 'ms_per_step': _r(f['ms_per_step']), 'kernel_ms': _r(f['roofline'].get('kernel_ms')),
@@ -914,7 +957,7 @@ def compact_line(out, detail_file=None):
     if len(line) >= COMPACT_LIMIT:      # never let an over-long string cost the round its measurement again
         for k in ('other_ms_per_step', 'forward_only'):
             c.pop(k, None)
-        c['roofline'].pop('per_kernel_ms', None)
+        c.get('roofline', {}).pop('per_kernel_ms', None)
         c['config']['workload'] = _short(c['config']['workload'], 80)
         if c.get('cpu_baseline'):
             c['cpu_baseline']['sample'] = _short(c['cpu_baseline']['sample'], 120)
@@ -932,6 +975,36 @@ def library_sha256():
         for chunk in iter(lambda: f.read(1 << 20), b''):
             h.update(chunk)
     return h.hexdigest()
+
+
+DUMP_LIMIT = 60 * 10 ** 6      # bytes of array data --dump-outputs writes at most: 64 MB with room for the .npy headers
+DUMP_SEED = 0
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT, seed=DUMP_SEED):
+    """Write {name: float32 / float64 array} as out_dir/<name>.npy.  Over `limit` bytes in all, the arrays whose leading dimension
+    is the largest one (the rollouts) keep the same rows: a sorted sample drawn with a fixed seed, as many as fit -- the same rows
+    in every run with the same arguments, whichever build of the project runs."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    lead = max((a.shape[0] for a in arrays.values() if a.ndim >= 2), default=0)
+    rows = None
+    if total > limit and lead:
+        big = sum(a.nbytes for a in arrays.values() if a.ndim >= 2 and a.shape[0] == lead)
+        k = int((limit - (total - big)) // (big // lead))
+        assert k >= 1, 'the outputs do not fit the dump limit even at one row each'
+        rows = np.sort(np.random.default_rng(seed).choice(lead, size=k, replace=False))
+    written = 0
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if rows is not None and a.ndim >= 2 and a.shape[0] == lead:
+            a = np.ascontiguousarray(a[rows])
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+        written += a.nbytes
+    assert written <= limit, written
+    sampled = f'; rows sampled: {len(rows)} of {lead} (seed {seed})' if rows is not None else ''
+    print(f'bench.py: wrote {len(arrays)} output arrays ({written / 2**20:.1f} MiB) to {out_dir}{sampled}', file=sys.stderr)
+    return rows
 
 
 def _free_port():
@@ -964,11 +1037,19 @@ def main():
     ap.add_argument('--points', type=int, default=0, help='override contact points')
     ap.add_argument('--integrator', type=int, default=1, help='1 = odeint-euler (reference default), 0 = dynamics()')
     ap.add_argument('--block', type=int, default=0)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-others', action='store_true', help='headline workload only (no forward_only / sweep / side workloads)')
+    ap.add_argument('--full', action='store_true',
+                    help='measure beyond the headline: roofline / per-kernel HIP-event figures, comm_ms, forward_only, sweeps, side workloads, '
+                         'cpu_baseline, and write the detail file')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without cpu_baseline')
+    ap.add_argument('--no-others', action='store_true', help='--full with the headline workload only (no forward_only / sweep / side workloads)')
     ap.add_argument('--detail', default=os.path.join(REPO, 'bench_detail.json'),
-                    help='where rank 0 writes the full record (per-kernel tables, batch sweep, side workloads, CPU legs); the stdout line stays < 4 KB')
+                    help='where rank 0 of a --full run writes the full record (per-kernel tables, batch sweep, side workloads, CPU legs); '
+                         'the stdout line stays < 4 KB')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     world_env = os.environ.get('WORLD_SIZE')
     if args.gpus > 1 and world_env is None:
@@ -981,10 +1062,14 @@ def main():
     if r.world > 1 and r.dist_world != args.gpus:
         print(f'bench.py: the process group has {r.dist_world} ranks, --gpus {args.gpus}', file=sys.stderr)
         sys.exit(2)
-    res, (N, T) = r.run(args.workload, args.steps, args.warmup, batch=args.batch)
+    res, (N, T) = r.run(args.workload, args.steps, args.warmup, batch=args.batch, measure=args.full,
+                        keep_outputs=bool(args.dump_outputs) and r.rank == 0)
+    outputs = res.pop('outputs', None)
+    if outputs is not None:
+        dump_outputs(outputs, args.dump_outputs)
     extras, others = {}, {}
-    full = args.workload == 'c3' and not args.no_others and not args.batch and not args.points
-    if full:
+    sides = args.full and args.workload == 'c3' and not args.no_others and not args.batch and not args.points
+    if sides:
         short = max(args.steps // 3, 5)
         f, _ = r.run('c3f', args.steps, args.warmup)
         extras['forward_only'] = {'value': f['value'], 'unit': 'rollout-steps/s', 'ms_per_step': f['ms_per_step'],
@@ -1035,23 +1120,20 @@ def main():
                'steps': res['steps'], 'warmup': res['warmup'], 'ms_per_step': res['ms_per_step'],
                'ms_per_step_ranks': res['ms_per_step_ranks'], 'comm_ms': res['comm_ms'],
                'higher_is_better': True, 'scaling': res['scaling'], 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-               'config': res['config'], 'roofline': res['roofline']}
+               'config': res['config'], **({'roofline': res['roofline']} if 'roofline' in res else {})}
         out.update(extras)
         if others:
             out['other_workloads'] = others
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(N, args.integrator, T, headline=args.workload) if not r.dist_on else None      # timed at N=1 only
         detail_file = None
-        try:
-            with open(args.detail, 'w') as f:
-                json.dump(out, f)
-            detail_file = os.path.relpath(args.detail, REPO) if os.path.abspath(args.detail).startswith(REPO + os.sep) else args.detail
-            scratch = os.path.join(REPO, 'gpurun_out')      # a copy where a gpurun call merges files back from
-            if os.path.isdir(scratch) and os.path.dirname(os.path.abspath(args.detail)) != scratch:
-                with open(os.path.join(scratch, os.path.basename(args.detail)), 'w') as f:
+        if args.full:
+            try:
+                with open(args.detail, 'w') as f:
                     json.dump(out, f)
-        except OSError as e:
-            print(f'bench.py: could not write {args.detail}: {e}', file=sys.stderr)
+                detail_file = os.path.relpath(args.detail, REPO) if os.path.abspath(args.detail).startswith(REPO + os.sep) else args.detail
+            except OSError as e:
+                print(f'bench.py: could not write {args.detail}: {e}', file=sys.stderr)
         line = compact_line(out, detail_file)
     if r.dist_on:
         import torch.distributed as dist

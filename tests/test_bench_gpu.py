@@ -6,6 +6,7 @@ import subprocess
 import sys
 import tempfile
 
+import numpy as np
 import pytest
 import torch
 
@@ -29,7 +30,7 @@ def _last_line_and_detail(r):
 def test_bench_spawns_its_own_ranks():
     """`bench.py --gpus 2` with no launcher around it starts two ranks itself and says so in the JSON line."""
     with tempfile.TemporaryDirectory() as td:
-        r = _run_bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '64', '--no-others', '--no-cpu-baseline',
+        r = _run_bench(['--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '64', '--full', '--no-others', '--no-cpu-baseline',
                         '--detail', os.path.join(td, 'd.json')], {'MF_BENCH_SINGLE_DEVICE': '1', 'MF_BENCH_BACKEND': 'gloo'})
         assert r.returncode == 0, r.stderr[-2000:]
         out, full = _last_line_and_detail(r)
@@ -88,3 +89,45 @@ def test_two_rank_terrain_gradient_equals_single_process():
     for k in ('gz', 'gmu'):
         scale = float(one[k].abs().max())
         assert scale > 0 and float((two[k] - one[k]).abs().max()) <= 2e-4 * scale, k
+
+
+def _dumped(d):
+    return {n[:-len('.npy')]: np.load(os.path.join(d, n)) for n in sorted(os.listdir(d))}
+
+
+def test_plain_run_times_its_steps_and_dumps_the_last_one():
+    """A plain run (no --full): the contract's keys for exactly `--steps` timed steps, no roofline / CPU baseline / detail file.
+    `--dump-outputs` writes what the fit step hands its caller -- the loss and the gradients of the terrain and friction maps -- and a
+    second run with the same arguments writes the same arrays (up to the order of the backward's float atomics)."""
+    B, T, K = 64, 500, 3
+    with tempfile.TemporaryDirectory() as td:
+        runs = []
+        for i in range(2):
+            d = os.path.join(td, f'out{i}')
+            r = _run_bench(['--gpus', '1', '--steps', str(K), '--warmup', '1', '--batch', str(B), '--dump-outputs', d,
+                            '--detail', os.path.join(td, 'detail.json')])
+            assert r.returncode == 0, r.stderr[-2000:]
+            line = json.loads(r.stdout.rstrip('\n').splitlines()[-1])
+            assert line['steps'] == K and line['warmup'] == 1 and line['higher_is_better'] is True and line['dtype'] == 'f32'
+            assert line['ms_per_step'] > 0 and abs(line['value'] - B * T / (line['ms_per_step'] * 1e-3)) <= 1e-4 * line['value']
+            assert 'roofline' not in line and 'cpu_baseline' not in line and line['detail'] is None
+            assert not os.path.exists(os.path.join(td, 'detail.json'))
+            runs.append(_dumped(d))
+    a, b = runs
+    assert set(a) == {'loss', 'grad_z', 'grad_mu'} and all(v.dtype == np.float32 for v in a.values())
+    assert a['loss'].shape == () and a['grad_z'].shape == a['grad_mu'].shape == (256, 256)
+    for k in a:
+        scale = float(np.abs(a[k]).max())
+        assert scale > 0 and float(np.abs(a[k] - b[k]).max()) <= 1e-5 * scale, k
+
+
+def test_dump_of_the_forward_holds_all_six_outputs():
+    """c3f (the forward alone, graph-replayed): the six outputs of the last timed step, as the module returns them."""
+    B = 32
+    with tempfile.TemporaryDirectory() as td:
+        r = _run_bench(['--gpus', '1', '--workload', 'c3f', '--steps', '2', '--warmup', '1', '--batch', str(B), '--dump-outputs', td])
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = _dumped(td)
+    assert set(out) == {'Xs', 'Xds', 'Rs', 'Om', 'Fs', 'Ff'} and all(v.dtype == np.float32 for v in out.values())
+    assert out['Xs'].shape == (B, 500, 3) and out['Rs'].shape == (B, 500, 3, 3) and out['Fs'].shape == (B, 500, 4, 3)
+    assert all(np.isfinite(v).all() for v in out.values()) and float(np.abs(out['Fs']).max()) > 0

@@ -73,3 +73,38 @@ def test_a_failed_side_workload_does_not_cost_the_line():
     line = bench.compact_line(rec, 'bench_detail.json')
     d = json.loads(line)
     assert len(line) < bench.COMPACT_LIMIT and d['other_ms_per_step'] == {'strong_c3': None} and abs(d['value'] - rec['value']) <= 1e-5 * rec['value']
+
+
+def test_compact_line_of_a_plain_run():
+    """A plain run (no --full) measures the headline only: no `roofline`, no `cpu_baseline`, no side workloads, no detail file."""
+    rec = _record()
+    for k in ('roofline', 'cpu_baseline', 'forward_only', 'other_workloads'):
+        rec.pop(k, None)
+    line = bench.compact_line(rec, None)
+    c = json.loads(line)
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup', 'config'):
+        assert k in c, k
+    assert 'roofline' not in c and 'cpu_baseline' not in c and c['detail'] is None and len(line) < bench.COMPACT_LIMIT
+    assert abs(c['ms_per_step'] - rec['ms_per_step']) <= 1e-5 * rec['ms_per_step']
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_the_limit(tmp_path):
+    """--dump-outputs: float arrays as <name>.npy; over the limit, every array led by the rollouts keeps the SAME seeded rows."""
+    import numpy as np
+    rng = np.random.default_rng(7)
+    B, T = 1024, 500
+    arrays = {'Xs': rng.random((B, T, 3), dtype=np.float32), 'Rs': rng.random((B, T, 3, 3), dtype=np.float32),
+              'Fs': rng.random((B, T, 4, 3), dtype=np.float32), 'Ff': rng.random((B, T, 4, 3), dtype=np.float32),
+              'loss': np.float64(1.5) * np.ones((), np.float64)}      # 74 MB: the c3f forward's outputs are 85 MB
+    rows = bench.dump_outputs(arrays, str(tmp_path / 'a'))
+    again = bench.dump_outputs(arrays, str(tmp_path / 'b'))
+    assert rows is not None and 0 < len(rows) < B and np.array_equal(rows, again) and np.all(np.diff(rows) > 0)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['Ff.npy', 'Fs.npy', 'Rs.npy', 'Xs.npy', 'loss.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 64 * 10 ** 6
+    for k, a in arrays.items():
+        got = np.load(tmp_path / 'a' / f'{k}.npy')
+        assert got.dtype == a.dtype and np.array_equal(got, a[rows] if a.ndim >= 2 else a), k
+    small = {'grad_z': arrays['Xs'][:4, :, 0].copy()}
+    assert bench.dump_outputs(small, str(tmp_path / 'c')) is None
+    assert np.array_equal(np.load(tmp_path / 'c' / 'grad_z.npy'), small['grad_z'])

@@ -1,6 +1,6 @@
 """BASELINE configs[4] (c5: 8192 rollouts in total + encoder, data-parallel) on the one-GPU rig, so that an 8-GPU run is not the
 first run of its code: `bench.py --workload c5` as two gloo ranks sharing GPU 0 and as ONE forced RCCL rank, the
-default multi-rank line (strong_c3 and c5 among its `other_workloads`), and the exchanged encoder gradients of a two-rank step
+--full multi-rank line (strong_c3 and c5 among its `other_workloads`), and the exchanged encoder gradients of a two-rank step
 -- launch by launch with the hooked bucket exchange, and replayed as two hipGraphs around the live exchange -- against the
 single-process gradients of both ranks' samples."""
 import json
@@ -22,7 +22,7 @@ def _bench(args, env_extra, timeout=1500):
     env.update(env_extra)
     with tempfile.TemporaryDirectory() as td:
         detail = os.path.join(td, 'detail.json')
-        r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py')] + args + ['--detail', detail], env=env, capture_output=True, text=True,
+        r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py')] + args + ['--full', '--detail', detail], env=env, capture_output=True, text=True,
                            timeout=timeout)
         assert r.returncode == 0, r.stderr[-3000:]
         last = r.stdout.rstrip('\n').splitlines()[-1]          # what the driver parses: the LAST stdout line, compact
@@ -66,7 +66,7 @@ def test_c5_eight_gloo_ranks_the_real_partition():
 
 
 def test_default_eight_rank_line_carries_strong_c3_and_c5():
-    """The DEFAULT command at N = 8 on the one-GPU rig: weak headline (1024 rollouts per rank, 8192 in total), `strong_c3`
+    """The --full command at N = 8 on the one-GPU rig: weak headline (1024 rollouts per rank, 8192 in total), `strong_c3`
     (8192 in total = 1024 per rank) and `c5` (8 x 1024 + one sample each) with their exchange times."""
     out = _bench(['--gpus', '8', '--steps', '3', '--warmup', '1', '--no-cpu-baseline'], {'MF_BENCH_SINGLE_DEVICE': '1', 'MF_BENCH_BACKEND': 'gloo', 'MF_BENCH_C5': '1'},
                  timeout=2400)
@@ -86,7 +86,7 @@ def test_c5_one_forced_rccl_rank():
 
 
 def test_default_multi_rank_line_carries_strong_c3_and_c5():
-    """The DEFAULT command at N = 2 (no --no-others): weak-scaling headline + forward_only + strong_c3 + c5."""
+    """The --full command at N = 2 (no --no-others): weak-scaling headline + forward_only + strong_c3 + c5."""
     out = _bench(['--gpus', '2', '--steps', '4', '--warmup', '2', '--no-cpu-baseline'], {'MF_BENCH_SINGLE_DEVICE': '1', 'MF_BENCH_BACKEND': 'gloo', 'MF_BENCH_C5': '1'})
     assert out['n_gpus'] == 2 and out['scaling'] == 'weak' and out['config']['rollouts_total'] == 2048
     ow = out['other_workloads']

@@ -115,7 +115,7 @@ def test_bench_through_its_multi_rank_code_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
     env.update({'MF_BENCH_FORCE_DIST': '1', 'HSA_ENABLE_IPC_MODE_LEGACY': '0'})
     r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '2', '--batch', '256',
-                        '--no-others', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
+                        '--full', '--no-others', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     last = r.stdout.rstrip('\n').splitlines()[-1]
     assert last.startswith('{') and len(last) < 4096, r.stdout[-600:]

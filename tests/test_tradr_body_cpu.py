@@ -11,7 +11,15 @@ import torch
 from oracle import dphysics_oracle as orc
 from tests import helpers as hp
 
-MESH = '/root/reference/monoforce/config/meshes/tradr.obj'
+
+@pytest.fixture(scope='module')
+def mesh(tmp_path_factory):
+    """The reference's tradr.obj as the loader sees it -- its 'v' lines, 8 decimals, rebuilt from tests/golden/tradr_mesh.npz -- in a
+    directory of its own."""
+    path = tmp_path_factory.mktemp('meshes') / 'tradr.obj'
+    with open(path, 'w') as f:
+        f.writelines('v %.8f %.8f %.8f\n' % tuple(r) for r in hp.load('tradr_mesh')['vertices'])
+    return str(path)
 
 
 def _sorted_rows(a):
@@ -27,12 +35,11 @@ def test_fixture_is_the_175_point_body():
     assert np.allclose(g['robot_size'], [1.152, 0.574], atol=5e-4)
 
 
-@pytest.mark.skipif(not os.path.exists(MESH), reason='the reference checkout (and its tradr.obj) is not on this box')
-def test_points_from_obj_on_the_reference_mesh():
+def test_points_from_obj_on_the_reference_mesh(mesh):
     """The mesh loader of the product (no open3d): same point SET, same masks per point, same robot_size as the fixture."""
     from monoforce_amd import dphys_config as dc
     g = hp.load('tradr_body')
-    pts = dc.points_from_obj(MESH, voxel_size=0.1)
+    pts = dc.points_from_obj(mesh, voxel_size=0.1)
     assert pts.dtype == torch.float32 and tuple(pts.shape) == (175, 3)
     assert np.abs(_sorted_rows(pts.numpy()) - _sorted_rows(g['points'])).max() <= 1e-6
     p, parts, size = dc.robot_geometry('tradr', pts)
@@ -42,13 +49,12 @@ def test_points_from_obj_on_the_reference_mesh():
     for m, mg in zip(parts, g['masks']):
         assert np.abs(_sorted_rows(p[m].numpy()) - _sorted_rows(g['points'][mg])).max() <= 1e-6
     # without down-sampling: every vertex of the file
-    assert dc.points_from_obj(MESH, voxel_size=None).shape[0] == int(g['n_vertices'])
+    assert dc.points_from_obj(mesh, voxel_size=None).shape[0] == int(g['n_vertices'])
 
 
-@pytest.mark.skipif(not os.path.exists(MESH), reason='the reference checkout (and its tradr.obj) is not on this box')
-def test_dphysconfig_finds_the_mesh_through_the_environment(monkeypatch):
+def test_dphysconfig_finds_the_mesh_through_the_environment(mesh, monkeypatch):
     from monoforce_amd.dphys_config import DPhysConfig
-    monkeypatch.setenv('MONOFORCE_MESH_DIR', os.path.dirname(MESH))
+    monkeypatch.setenv('MONOFORCE_MESH_DIR', os.path.dirname(mesh))
     cfg = DPhysConfig(robot='tradr')
     assert cfg.robot_points.shape == (175, 3) and [int(m.sum()) for m in cfg.driving_parts] == [45, 45]
     assert cfg.robot_mass == 40.0 and abs(float(cfg.robot_size[1]) - 0.5736) < 1e-3

@@ -5,8 +5,8 @@ TAG=${1:-rX}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT /tmp/mfprof      # (raw traces stay on the box under /tmp: gpurun_out/ is capped at 64 MiB; only summaries are written to $OUT)
 export TMPDIR=/tmp
-B="--no-cpu-baseline --no-others"
-timeout 900 python bench.py --detail $OUT/${TAG}_bench_default_detail.json > $OUT/${TAG}_bench_default.json 2> $OUT/bench_default.err      # (stdout: the compact line the driver parses; --detail: tables, sweep, side workloads)
+B="--full --no-cpu-baseline --no-others"
+timeout 900 python bench.py --full --detail $OUT/${TAG}_bench_default_detail.json > $OUT/${TAG}_bench_default.json 2> $OUT/bench_default.err      # (stdout: the compact result line; --detail: tables, sweep, side workloads)
 for w in c3f c3 c4 ref_nb; do
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/mfprof/prof_$w -o $w -- python bench.py --steps 20 --warmup 3 --workload $w $B --detail $OUT/${TAG}_${w}_bench_under_rocprof_detail.json > $OUT/${TAG}_${w}_bench_under_rocprof.json 2> $OUT/prof_$w.err
   f=$(find /tmp/mfprof/prof_$w -name "*kernel_stats.csv" | head -1)

@@ -5,8 +5,8 @@ TAG=${1:-rX}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT /tmp/mfprof
 export TMPDIR=/tmp
-B="--no-cpu-baseline --no-others"
-timeout 900 python bench.py --detail $OUT/${TAG}_bench_default_detail.json > $OUT/${TAG}_bench_default.json 2> $OUT/bench_default.err      # (stdout: the compact line the driver parses; --detail: tables, sweep, side workloads)
+B="--full --no-cpu-baseline --no-others"
+timeout 900 python bench.py --full --detail $OUT/${TAG}_bench_default_detail.json > $OUT/${TAG}_bench_default.json 2> $OUT/bench_default.err      # (stdout: the compact result line; --detail: tables, sweep, side workloads)
 for w in c3f c3; do
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/mfprof/prof_$w -o $w -- python bench.py --steps 20 --warmup 3 --workload $w $B --detail $OUT/${TAG}_${w}_bench_under_rocprof_detail.json > $OUT/${TAG}_${w}_bench_under_rocprof.json 2> $OUT/prof_$w.err
   f=$(find /tmp/mfprof/prof_$w -name "*kernel_stats.csv" | head -1)
@@ -64,5 +64,5 @@ json.dump(res, open(f'{out}/hbm_traffic.json', 'w'), indent=1)
 print(json.dumps(res))
 PY
 cp $OUT/hbm_traffic.json profiles/hbm_traffic.json
-timeout 400 python bench.py --detail $OUT/${TAG}_bench_default_with_traffic_detail.json > $OUT/${TAG}_bench_default_with_traffic.json 2> /dev/null
+timeout 400 python bench.py --full --detail $OUT/${TAG}_bench_default_with_traffic_detail.json > $OUT/${TAG}_bench_default_with_traffic.json 2> /dev/null
 ls $OUT
