@@ -37,18 +37,25 @@ namespace mf {
 // the compiler instead of run one stream after the other, and slower: 0.399 vs 0.367 ms (dynamics(): 0.548 vs 0.448).
 enum { kCpEarly = 0, kCpLate = 1, kCpSaved = 2, kCpStream = 3 };
 #ifdef MF_STREAM_PROFILE      // A/B build: where the waves of the streaming backward spend their cycles (tools/stream_profile.py)
-extern __device__ unsigned long long mf_stream_prof[16];
+extern __device__ unsigned long long mf_stream_prof[32];
 #define MF_PROF_T(v) const unsigned long long v = __builtin_readcyclecounter()
+#define MF_PROF_RT(v) const unsigned long long v = __builtin_amdgcn_s_memrealtime()      // (100 MHz, the same on every CU)
 #define MF_PROF_ACC(name) unsigned long long name = 0
 #define MF_PROF_SUM(name, t0) name += __builtin_readcyclecounter() - (t0)
 #define MF_PROF_OUT(slot, val) do { if (lane == 0) atomicAdd(&mf_stream_prof[slot], (unsigned long long)(val)); } while (0)
 #define MF_PROF_ADD(slot, t0) MF_PROF_OUT(slot, __builtin_readcyclecounter() - (t0))
+#define MF_PROF_MAX(slot, val) do { if (lane == 0) atomicMax(&mf_stream_prof[slot], (unsigned long long)(val)); } while (0)
+// (the tail's stamps wait for this wave's memory operations first: a segment then holds its own round trips)
+#define MF_PROF_DRAIN() asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory")
 #else
 #define MF_PROF_T(v)
+#define MF_PROF_RT(v)
 #define MF_PROF_ACC(name)
 #define MF_PROF_SUM(name, t0)
 #define MF_PROF_OUT(slot, val)
 #define MF_PROF_ADD(slot, t0)
+#define MF_PROF_MAX(slot, val)
+#define MF_PROF_DRAIN()
 #endif
 #ifdef MF_NO_WPE      // A/B build: no register limit on the streaming kernels
 #define MF_STREAM_WPE
@@ -73,6 +80,7 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
   using Msk = typename MaskOf<S>::type;
   constexpr unsigned kS = (unsigned)sizeof(S), kC = 2u * kS;      // bytes of a scalar / of a control row (v, w)
   const int lane = threadIdx.x & 63;
+  MF_PROF_T(t_k0); MF_PROF_RT(rt_k0);
   const int tid = STREAM ? blockIdx.x * 64 + lane : blockIdx.x * blockDim.x + threadIdx.x;
   const int b = tid >> 4;
   __shared__ S win[WIN ? 2 * kWinW * kWinW : 1];
@@ -257,6 +265,10 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
     if constexpr (WIN) {
       if (win_emit(win, win_flat0, win_shift, (unsigned)(a.H - 1), idx, vz, vm, want_gmu)) return;
     }
+#ifdef MF_STREAM_NO_ATOMIC      // A/B build: the cell gradients are dropped (wrong results; time only)
+    asm volatile("" :: "v"(vz), "v"(vm), "v"(idx));
+    return;
+#endif
     atomic_add(at32(gzmap, goff + idx), vz);
     if (want_gmu) atomic_add(at32(gmumap, goff + idx), vm);
   };
@@ -500,6 +512,26 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
     }
   };
 
+  // the adjoint-independent part of the terrain snap of the initial height (after the loop): the footprint cell of the initial pose,
+  // its bilinear weight and the two weighted height sums
+  auto snap_cell = [&](int& idx, S& wq, S& dx, S& dy) {
+    const S Ra = a.R0[b * 9 + cc * 3 + 0], Rb = a.R0[b * 9 + cc * 3 + 1], Rc = a.R0[b * 9 + cc * 3 + 2];
+    const S x0c = a.x_init[b * 3 + cc];
+    const S pc = (P0 * Ra + P1 * Rb + P2 * Rc) + x0c;
+    const S lim = S(262144.0);
+    const S uq = M::cell_coord(pc, a.d_max, a.res, a.inv_res);
+    const int ui = (int)M::clamp(uq, -lim, lim);
+    const S fr = uq - (S)ui;
+    const int base = dppi<kB1>(ui) + __mul24(a.H, dppi<kB0>(ui));
+    idx = min(max(base + cell_off, 0), last);
+    const S wa = mf_fma(wa_s, dpp<kB0>(fr), wa_o), wb = mf_fma(wb_s, dpp<kB1>(fr), wb_o);
+    const S zc = ld32(zmap, moff + (unsigned)idx);
+    wq = wa * wb;
+    dx = dot4(zc, wa_s * wb); dy = dot4(zc, wb_s * wa);
+  };
+  int snap_idx = 0;
+  S snap_wq = zero, snap_dx = zero, snap_dy = zero;
+
   StateIn sA, sB;
   UpIn uA, uB;
   Rec recA, recB;
@@ -647,23 +679,30 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
       constexpr int kSlots = SLOTS, kPlanesD = ODE ? 0 : 6, kPlanes = (XS_ONLY ? 10 : 12) + kPlanesD;      // dynamics(): six more (struct CoefD)
       constexpr bool kPow2 = (kSlots & (kSlots - 1)) == 0;
       __shared__ f4v ring[kSlots * kPlanes * 64];
-      __shared__ int flags[2];
+      __shared__ int flags[4];      // steps written, steps read; loss-value shares in l_part (fused loss value); the snap's cell in snap_c
       typedef __attribute__((address_space(3))) volatile int LdsCounter;      // (a generic volatile pointer would make FLAT accesses)
       LdsCounter* vflags = (LdsCounter*)flags;
-      if (threadIdx.x == 0) { flags[0] = 0; flags[1] = 0; }
+      if (threadIdx.x == 0) { flags[0] = 0; flags[1] = 0; flags[2] = 0; flags[3] = 0; }
       __syncthreads();
       // MF_LOSS_VALUE_IN_BACKWARD: the loss VALUE as well.  The fetching waves add up the weighted squared errors of the stamped rows
       // they convert into dL/dXs anyway (the computing wave row 0's); at the end one partial sum per workgroup in a fixed order, and the
       // workgroup that takes the last ticket adds the partial sums in index order (as rollout_fwd_cp_kernel.h's LOSS kernels do).
+      // None of it waits for the adjoint: the computing wave leaves its share in l_part before its first step, and fetching wave 0 does
+      // the rest once the other fetching wave's share is there -- while the computing wave still works through the last steps in the ring.
       const bool loss_val = loss_on && a.loss_out != nullptr;      // wave-uniform
-      __shared__ S l_part[3 * 16 + 64];
-      auto loss_value_finish = [&](S acc) {     // every wave of the workgroup, once
+      __shared__ S l_part[3 * 16];
+      auto loss_share = [&](S acc) {            // every wave of the workgroup, once: this wave's share, then counted
         if (!loss_val) return;
         const int wv = (int)(threadIdx.x >> 6);
         if (lane < 16) l_part[wv * 16 + lane] = zero;             // (LDS executes a wave's operations in order)
         if (p == 0 && q < 3) l_part[wv * 16 + (lane >> 4) * 4 + q] = acc;
-        __syncthreads();
-        if (wv != 0) return;
+        asm volatile("" ::: "memory");
+        if (lane == 0) __hip_atomic_fetch_add(&flags[2], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);      // (lane 0 is always live)
+      };
+      auto loss_value_finish = [&]() {          // fetching wave 0, after its own share
+        if (!loss_val) return;
+        while (__builtin_amdgcn_readfirstlane(vflags[2]) != 3) __builtin_amdgcn_s_sleep(1);
+        asm volatile("" ::: "memory");
         unsigned last_wg = 0u;
         if (lane == 0) {
           S tot = zero;
@@ -679,17 +718,42 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         if (last_wg) {                                            // every workgroup has written its partial sum: the mean, in index order
           __threadfence();
           const int n_act = min(64, (a.B - (int)blockIdx.x * 4) * 16);      // live lanes of this (possibly trailing) workgroup: the first n_act
+          // lane l adds the partial sums l, l + n_act, l + 2 n_act, ... in that order, then the lanes' sums are added in lane order -- eight
+          // requests in flight at a time instead of one round trip per partial sum, and no serial loop over LDS.  The padding adds +0,
+          // which changes no bits: both sums start at +0 and a sum of finite values rounded to nearest is never -0.
           S tot = zero;
-          for (unsigned k2 = (unsigned)lane; k2 < gridDim.x; k2 += (unsigned)n_act) tot += __builtin_nontemporal_load(a.loss_partial + k2);
-          l_part[48 + lane] = tot;
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (one wave: its LDS operations execute in order)
+          for (unsigned k0 = (unsigned)lane; k0 < gridDim.x; k0 += 8u * (unsigned)n_act) {
+            S v[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+              const unsigned k2 = k0 + (unsigned)(i * n_act);
+              v[i] = __builtin_nontemporal_load(a.loss_partial + min(k2, gridDim.x - 1u));
+              v[i] = k2 < gridDim.x ? v[i] : zero;
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) tot += v[i];
+          }
+          S sum = zero;
+#pragma unroll
+          for (int k2 = 0; k2 < 64; ++k2) sum += k2 < n_act ? mf_readlane(tot, k2) : zero;
           if (lane == 0) {
-            S sum = zero;
-            for (int k2 = 0; k2 < n_act; ++k2) sum += l_part[48 + k2];
             a.loss_out[0] = sum * a.loss_inv_count;
             *a.loss_ticket = 0u;
           }
         }
+      };
+      // The terrain snap of the initial height (after the loop, below) needs the adjoint only as a factor: the footprint cell of the initial
+      // pose, its weights and the two height-weighted sums are prepared by fetching wave 1 once its steps are in the ring.
+      __shared__ S snap_c[4 * 64];
+      auto snap_prepare = [&]() {               // fetching wave 1
+        if (!a.skip_snap) {
+          S wq, dx, dy;
+          int idx;
+          snap_cell(idx, wq, dx, dy);
+          snap_c[lane] = idx_as(zero, idx); snap_c[64 + lane] = wq; snap_c[128 + lane] = dx; snap_c[192 + lane] = dy;
+        }
+        asm volatile("" ::: "memory");
+        vflags[3] = 1;
       };
       if (threadIdx.x >= 64) {
         // ---------------- the two fetching waves ----------------
@@ -744,16 +808,29 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           asm volatile("" ::: "memory");
           MF_PROF_SUM(acc_room, t0);
         };
-        auto publish = [&](int from, int upto) {    // steps [from, upto) are in the ring: in order behind the other wave's
+        // Steps are published in order: `pub` is the first step of this wave's batch that is written but not yet published.  After each
+        // write the wave publishes what it has if the other wave's steps before them are out (its turn), and goes on to the next step
+        // of its batch if they are not; only at the end of a batch does it wait for its turn.  (Waiting for the turn after every step
+        // held each wave's second and third rebuild of a batch behind the other wave's batch: the two fetching waves took turns
+        // instead of rebuilding side by side.)
+        int pub = 0;
+        auto publish_written = [&](int upto) {      // steps [pub, upto) are in the ring: publish them if it is this wave's turn
+          asm volatile("" ::: "memory");
+          if (__builtin_amdgcn_readfirstlane(vflags[0]) == pub) { vflags[0] = upto; pub = upto; }
+        };
+        auto publish = [&](int upto) {              // ... and wait for the turn if it is not
           asm volatile("" ::: "memory");
           MF_PROF_T(t0);
-          while (__builtin_amdgcn_readfirstlane(vflags[0]) != from) __builtin_amdgcn_s_sleep(1);
-          asm volatile("" ::: "memory");
+          if (pub != upto) {
+            while (__builtin_amdgcn_readfirstlane(vflags[0]) != pub) __builtin_amdgcn_s_sleep(1);
+            asm volatile("" ::: "memory");
+            vflags[0] = upto; pub = upto;
+          }
           MF_PROF_SUM(acc_pub, t0);
-          vflags[0] = upto;
         };
         // (per step: everything is computed BEFORE the wave asks for room in the ring, the ten writes follow the grant, and the step is
-        //  published at once -- with whole batches behind one grant the computing wave idled 9 % of its time while a batch was rebuilt)
+        //  published at once when it is this wave's turn -- with whole batches behind one grant the computing wave idled 9 % of its time
+        //  while a batch was rebuilt)
         auto put = [&](const Slot& r, unsigned slot, int o) {
             Rec k;
             rebuild(r.st, r.sv, k);
@@ -820,7 +897,10 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
               constexpr int D0 = (XS_ONLY ? 10 : 12) * 64;
               out[D0] = d0; out[D0 + 64] = d1; out[D0 + 128] = d2; out[D0 + 192] = d3; out[D0 + 256] = d4; out[D0 + 320] = d5;
             }
-            publish(o, o + 1);
+            publish_written(o + 1);
+#ifdef MF_STREAM_PROFILE
+            if (o == 0) MF_PROF_ADD(18, t_k0);
+#endif
           };
         int ord = BATCH * fk;                       // ordinal of the first step of this wave's next batch to WRITE
         unsigned sbase = kB * (unsigned)fk;         // ... and its ring slot: (BATCH j) mod kSlots
@@ -838,8 +918,10 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           for (int i = 0; i < BATCH; ++i) gather1(s[i]);
         };
         auto put3 = [&](const Slot (&s)[BATCH]) {
+          pub = ord;
 #pragma unroll
           for (int i = 0; i < BATCH; ++i) put(s[i], sbase + (unsigned)i, ord + i);
+          publish(ord + BATCH);
           ord += 2 * BATCH;
           if constexpr (kSlots != 2 * BATCH) sbase = sbase + 2u * kB >= (unsigned)kSlots ? sbase + 2u * kB - (unsigned)kSlots : sbase + 2u * kB;
         };
@@ -868,13 +950,27 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
             Slot r0;
             fetch(r0);
             gather1(r0);
+            pub = o;
             put(r0, sl, o);
+            publish(o + 1);
             ++sl; ++o;
           }
         }
         MF_PROF_ADD(2 + 4 * fk, t_fetcher);
         MF_PROF_OUT(0 + 4 * fk, acc_room); MF_PROF_OUT(1 + 4 * fk, acc_pub);
-        loss_value_finish(l_acc);
+        loss_share(l_acc);
+        if (fk == 0) {
+          MF_PROF_T(t_lf);
+          loss_value_finish();
+          MF_PROF_DRAIN();
+          MF_PROF_ADD(21, t_lf);
+#ifdef MF_STREAM_PROFILE
+          MF_PROF_MAX(17, __builtin_readcyclecounter() - t_lf);
+          MF_PROF_MAX(14, __builtin_amdgcn_s_memrealtime());
+#endif
+        } else {
+          snap_prepare();
+        }
         return;
       }
         // ---------------- the computing wave ----------------
@@ -889,6 +985,7 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           l_row0 = stamped ? cp_loss_term(uZ.gXs, g0, w0) : zero;
           uZ.gXs = stamped ? cp_loss_grad(loss_scale, uZ.gXs, g0, w0) : zero;
         }
+        loss_share(l_row0);
         // The coefficients of a step's vector-Jacobian product, as the fetching wave leaves them in the ring.  With
         // cs = c / sum c, the gates mG, mF1 (1 / 0) and d1 = gFr . (mF1 n) -- the one lane sum that serves F0 = -A n and n both:
         struct Coef {
@@ -908,12 +1005,21 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         //  instruction each, ~14 cycles of this wave)
         MF_PROF_T(t_compute);
         MF_PROF_ACC(acc_wait);
+#ifdef MF_STREAM_PROFILE
+        unsigned long long acc_wait_early = 0, acc_wait_late = 0, n_waited = 0;
+#endif
         auto ensure = [&](int k) {                    // until k more steps are in the ring
           MF_PROF_T(t0);
           int have = __builtin_amdgcn_readfirstlane(seen);
           while (have < consumed + k) have = __builtin_amdgcn_readfirstlane(vflags[0]);
           asm volatile("" ::: "memory");
           MF_PROF_SUM(acc_wait, t0);
+#ifdef MF_STREAM_PROFILE
+          const unsigned long long dt = __builtin_readcyclecounter() - t0;
+          if (consumed < 30) acc_wait_early += dt;
+          if (consumed >= n_steps - 30) acc_wait_late += dt;
+          n_waited += __builtin_amdgcn_readfirstlane(seen) < consumed + k ? 1u : 0u;
+#endif
         };
         auto grab = [&](Coef& c, UpIn& up) {          // the next step out of the ring (it is there: ensure)
           const f4v* o = ring + (kPow2 ? (unsigned)(consumed & (kSlots - 1)) : rslot) * (unsigned)(kPlanes * 64) + lane;
@@ -1077,6 +1183,7 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         Coef cA, cB;
         if (n_steps > 0) {
           take(cA, uA);
+          MF_PROF_ADD(3, t_k0); MF_PROF_OUT(19, acc_wait);
           using single = std::integral_constant<int, 0>;
           for (; n >= 2; n -= 2) {
             ensure(2);
@@ -1088,7 +1195,19 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         }
         MF_PROF_ADD(9, t_compute);
         MF_PROF_OUT(8, acc_wait);
-        loss_value_finish(l_row0);
+#ifdef MF_STREAM_PROFILE
+        MF_PROF_OUT(22, acc_wait_early); MF_PROF_OUT(23, n_waited); MF_PROF_OUT(24, acc_wait_late);
+#endif
+        MF_PROF_ADD(20, t_k0);
+        MF_PROF_DRAIN();
+        MF_PROF_T(t_sw);
+        if (!a.skip_snap) {                           // (ready long before: fetching wave 1 prepared it after its last step)
+          while (__builtin_amdgcn_readfirstlane(vflags[3]) == 0) __builtin_amdgcn_s_sleep(1);
+          asm volatile("" ::: "memory");
+          snap_idx = idx_of(snap_c[lane]); snap_wq = snap_c[64 + lane]; snap_dx = snap_c[128 + lane]; snap_dy = snap_c[192 + lane];
+        }
+        MF_PROF_DRAIN();
+        MF_PROF_ADD(7, t_sw);
         uA = uZ; uB = uZ;                             // (the epilogue reads whichever the last iteration would have requested into)
     } else {
       // MODE = kCpSaved: ONE wave reads the record itself (either integrator; launches the streaming form does not cover, and the
@@ -1177,6 +1296,7 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
   if (n == 0) body(0, recA, recB, sB, sA, uA, uB);
   }
   // the upstream gradient of output row 0 sits in the buffer the last iteration prefetched into
+  MF_PROF_T(t_e0);
   UpIn up = (n_steps & 1) ? uB : uA;
   flush_stash();
   if constexpr (GCTRL) bstore2(rGctrl, v_ctrl, gctrl_pending, gv_pending, gwc_pending);
@@ -1187,24 +1307,17 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
   }
   lx = sum_points(lx); lxd = sum_points(lxd); lw = sum_points(lw);      // the adjoint of the initial state proper
   lR0 = sum_points(lR0); lR1 = sum_points(lR1); lR2 = sum_points(lR2);
+  MF_PROF_DRAIN();
+  MF_PROF_ADD(10, t_e0);
+  MF_PROF_T(t_s0);
 
   // terrain snap of the initial height: x.z = mean_i blend(z; cell((R0 P_i + x0).xy))   (dphysics.py:567-571)
   S gx0 = lx;
   if (!a.skip_snap) {
-    const S Ra = a.R0[b * 9 + cc * 3 + 0], Rb = a.R0[b * 9 + cc * 3 + 1], Rc = a.R0[b * 9 + cc * 3 + 2];
-    const S x0c = a.x_init[b * 3 + cc];
+    if constexpr (!STREAM) snap_cell(snap_idx, snap_wq, snap_dx, snap_dy);      // (the streaming form: prepared by a fetching wave)
     const S g = dpp<kB2>(lx) / (S)a.N;
-    const S pc = (P0 * Ra + P1 * Rb + P2 * Rc) + x0c;
-    const S lim = S(262144.0);
-    const S uq = M::cell_coord(pc, a.d_max, a.res, a.inv_res);
-    const int ui = (int)M::clamp(uq, -lim, lim);
-    const S fr = uq - (S)ui;
-    const int base = dppi<kB1>(ui) + __mul24(a.H, dppi<kB0>(ui));
-    const int idx = min(max(base + cell_off, 0), last);
-    const S wa = mf_fma(wa_s, dpp<kB0>(fr), wa_o), wb = mf_fma(wb_s, dpp<kB1>(fr), wb_o);
-    const S zc = ld32(zmap, moff + (unsigned)idx);
-    if (act) atomic_add(at32(gzmap, goff + (unsigned)idx), g * (wa * wb));
-    const S gpx = dot4(zc, wa_s * wb) * g * a.inv_res, gpy = dot4(zc, wb_s * wa) * g * a.inv_res;
+    if (act) atomic_add(at32(gzmap, goff + (unsigned)snap_idx), g * snap_wq);
+    const S gpx = snap_dx * g * a.inv_res, gpy = snap_dy * g * a.inv_res;
     S gpxy = q == 0 ? gpx : (q == 1 ? gpy : zero);
     gpxy = act ? gpxy : zero;
     gx0 = (q < 2 ? lx : zero) + sum_points(gpxy);        // the caller's x0.z is overwritten, so nothing flows to it
@@ -1216,6 +1329,16 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
     a.gw0[b * 3 + cc] = lw;
     a.gR0[b * 9 + cc * 3 + 0] = lR0; a.gR0[b * 9 + cc * 3 + 1] = lR1; a.gR0[b * 9 + cc * 3 + 2] = lR2;
   }
+#ifdef MF_STREAM_PROFILE
+  if constexpr (STREAM) {
+    MF_PROF_DRAIN();
+    MF_PROF_ADD(11, t_s0);
+    MF_PROF_RT(rt_end);
+    MF_PROF_ADD(12, t_k0);
+    MF_PROF_MAX(13, __builtin_readcyclecounter() - t_k0);
+    MF_PROF_MAX(14, rt_end); MF_PROF_MAX(15, ~rt_k0); MF_PROF_OUT(16, rt_end - rt_k0);
+  }
+#endif
   if constexpr (WIN) {
     __syncthreads();
     win_close(a, win, wx0, wy0);

@@ -4,10 +4,10 @@
 #include "rollout_bwd_cp_kernel.h"
 
 #ifdef MF_STREAM_PROFILE
-namespace mf { __device__ unsigned long long mf_stream_prof[16]; }
-extern "C" int mf_debug_stream_profile(unsigned long long* out16, int reset) {
-  if (out16) { if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(mf::mf_stream_prof), sizeof(mf::mf_stream_prof)) != hipSuccess) return 1; }
-  if (reset) { unsigned long long z[16] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(mf::mf_stream_prof), z, sizeof(z)) != hipSuccess) return 2; }
+namespace mf { __device__ unsigned long long mf_stream_prof[32]; }
+extern "C" int mf_debug_stream_profile(unsigned long long* out32, int reset) {
+  if (out32) { if (hipMemcpyFromSymbol(out32, HIP_SYMBOL(mf::mf_stream_prof), sizeof(mf::mf_stream_prof)) != hipSuccess) return 1; }
+  if (reset) { unsigned long long z[32] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(mf::mf_stream_prof), z, sizeof(z)) != hipSuccess) return 2; }
   return 0;
 }
 #endif
