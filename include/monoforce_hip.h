@@ -439,6 +439,41 @@ int mf_interpolate_grid_f32(const MfInterpDesc* desc, const float* grid, const f
 int mf_interpolate_grid_f64(const MfInterpDesc* desc, const double* grid, const double* xq, const double* yq, double* z_out, double* n_out,
                             int32_t* cells_out, double* frac_out, void* hip_stream);
 
+/* ---- MPPI trajectory optimiser around the path-cost rollout (no reference equivalent: the reference's node scores constant (v, w)
+ * samples once and takes argmin, monoforce_node.py:41-126) --------------------------------------------------------------------------
+ * One iteration: perturb the nominal control sequence, roll the B sequences out (mf_rollout_fwd_f32 in path-cost mode), score them,
+ * replace the nominal by the softmin-weighted average of the sequences.  Float32; plain device pointers (8-byte aligned where they hold
+ * (v, w) pairs); every entry validates before its first launch and never synchronises. */
+typedef struct MfMppiDesc {
+  int32_t B, T;                        /* sampled sequences, steps */
+  int32_t keep_nominal, reserved;      /* 1: sequence 0 carries no noise */
+  int64_t row_stride_b, row_stride_t;  /* cost rows: rows[b*sb + t*st + k], k < 4 (elements) */
+  int64_t x_stride_b;                  /* final poses: x_last[b*x_stride_b + c] */
+  float sigma[2], lo[2], hi[2];        /* noise scale and control limits for (v, w) */
+  float w_incl, w_force, w_goal, lambda;
+} MfMppiDesc;
+/* controls[b][t][k] = min(max(nominal[t][k] + sigma[k] * noise[b][t][k], lo[k]), hi[k]) -- multiply, add, clamp, each rounded like the
+ * ATen ops they replace; with keep_nominal row 0 is clamp(nominal) (its noise is not read).  One launch. */
+int mf_mppi_perturb_f32(const MfMppiDesc* desc, const float* nominal /* [T][2] */, const float* noise /* [B][T][2] */,
+                        float* controls /* [B][T][2] */, void* hip_stream);
+/* Path costs of B rollouts from the rows the path-cost rollout wrote (MfRolloutFwdBufs.cost_rows, either layout through the strides; the
+ * time-major one is read with one 16-byte load per rollout-step):
+ *   incl  = mean_t |atan2(r1, r2)| + mean_t |asin(clamp(-r0, -1, 1))|     (planner.costs_from_rows; diff_physics.py:263-266)
+ *   force = force_cost[b]                                                  (MfRolloutFwdBufs.path_cost; NULL iff w_force == 0: term 0)
+ *   goal  = |x_last[b][0:2] - goal|                                        (goal: two floats in DEVICE memory)
+ *   costs[b] = w_incl incl + w_force force + w_goal goal;   terms[b] = (incl, force, goal)   (terms may be NULL)
+ * The sum over t has a fixed order for a given (B, T); non-finite rows propagate by IEEE rules.  One launch. */
+int mf_path_costs_f32(const MfMppiDesc* desc, const float* cost_rows, const float* force_cost, const float* x_last, const float* goal,
+                      float* costs, float* terms, void* hip_stream);
+/* Softmin update over the FINITE costs: c_min their minimum, weights[b] = exp(-(c_b - c_min) / lambda) / sum (exactly 0 for a non-finite
+ * cost), nominal_out[t][k] = sum_b weights[b] controls[b][t][k]; best[0] = index of the first minimum among the finite costs (-1: none),
+ * n_valid[0] = their number; with none, nominal_out = nominal_in and all weights are 0.  nominal_out may be nominal_in.  Three launches
+ * (statistics in one workgroup, partial sums over 64-rollout chunks, their sum); every sum has a fixed order: results are bit-identical
+ * from call to call.  scratch: mf_mppi_scratch_bytes(desc) bytes, 8-byte aligned (-1 on a bad descriptor). */
+long long mf_mppi_scratch_bytes(const MfMppiDesc* desc);
+int mf_mppi_update_f32(const MfMppiDesc* desc, const float* costs, const float* controls, const float* nominal_in, float* weights,
+                       float* nominal_out, int32_t* best, int32_t* n_valid, void* scratch, long long scratch_bytes, void* hip_stream);
+
 /* Text of the calling thread's last error ("" if none).  THREAD-LOCAL: host threads driving different streams each read the message
  * of their own failed call (the reference raises a Python exception in the calling thread, dphysics.py:575,579 asserts). */
 const char* mf_last_error(void);

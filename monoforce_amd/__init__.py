@@ -17,4 +17,10 @@ def __getattr__(name):
     if name == 'LiftSplatShoot':
         from .terrain_encoder import LiftSplatShoot
         return LiftSplatShoot
+    if name == 'TrajectoryShooter':
+        from .planner import TrajectoryShooter
+        return TrajectoryShooter
+    if name == 'MPPIPlanner':
+        from .mppi import MPPIPlanner
+        return MPPIPlanner
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -68,5 +68,6 @@ extern "C" int mf_sizeof(const char* name) {
   if (!strcmp(name, "MfStageDesc")) return (int)sizeof(MfStageDesc);
   if (!strcmp(name, "MfInterpDesc")) return (int)sizeof(MfInterpDesc);
   if (!strcmp(name, "MfRolloutLoss")) return (int)sizeof(MfRolloutLoss);
+  if (!strcmp(name, "MfMppiDesc")) return (int)sizeof(MfMppiDesc);
   return -1;
 }

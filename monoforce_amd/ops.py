@@ -14,6 +14,10 @@ Schemas (tensors on the GPU, float32 or float64; `Bz` in {1, B}: a [1,H,W] map i
     monoforce::bev_splat_plan(Tensor geom, float[] dx, float[] bx, int[] nx) -> Tensor plan
     monoforce::bev_splat_fwd(Tensor x, Tensor plan, int B, int n_per_sample, float[] dx, float[] bx, int[] nx) -> Tensor
     monoforce::bev_splat_bwd(Tensor grad, Tensor plan, int B, int n_per_sample, int C, float[] dx, float[] bx, int[] nx) -> Tensor
+    monoforce::mppi_perturb(Tensor nominal, Tensor noise, float[] sigma, float[] lo, float[] hi, bool keep_nominal) -> Tensor controls
+    monoforce::path_costs(Tensor cost_rows, Tensor? force_cost, Tensor x_last, Tensor goal, float[] weights) -> (Tensor costs, Tensor terms)
+    monoforce::mppi_update(Tensor costs, Tensor controls, Tensor nominal, float lam)
+                                 -> (Tensor nominal, Tensor weights, Tensor best, Tensor n_valid)
 
 `consts` = [mass, gravity, stiffness, damping, grid_res, d_max, dt, omega_max, robot_size_y(, traj_sim_time)]; `part_id[N]` int32
 (index of the last driving mask holding the point, -1 = not driving); `Iinv` [3,3] on the HOST (nine scalars of the launch
@@ -24,6 +28,11 @@ and `rollout()` below copies it into the caller's tensor.  Outputs are `[B,T,...
 the current stream; no synchronisation, no host round trip, so they can be captured into a hipGraph.  Autograd formulas are
 registered (`rollout_fwd` -> `rollout_bwd`, `bev_splat_fwd` -> `bev_splat_bwd`), as are shape functions for tracing.  `rec` is
 the per-step record small launches keep for the backward (MfRolloutFwdBufs.rec; empty otherwise).
+
+The three MPPI ops (float32, no autograd; monoforce_amd/mppi.py is their consumer): `nominal` [T,2], `noise` / `controls` [B,T,2], `cost_rows`
+[B,T,4] in any strides whose last axis is dense (the [B,T,4] view `DPhysics.rollout_costs` returns is read in place), `x_last` [B,>=2], `goal`
+[2] on the device, `weights` = (inclination, force, goal) with `force_cost` given exactly when the force weight is non-zero; `best` / `n_valid`
+are int32 [1] on the device.
 
 `DPhysics` itself keeps calling the C ABI through its own autograd function (monoforce_amd/dphysics.py) -- same library calls,
 more options (articulated bodies, path costs, strided controls); `rollout()` / `splat()` below are the functional entries.
@@ -55,6 +64,9 @@ _L.define('dphys_rollout_bwd(Tensor z, Tensor? mu, Tensor controls, Tensor x_ini
 _L.define('bev_splat_plan(Tensor geom, float[] dx, float[] bx, int[] nx) -> Tensor')
 _L.define('bev_splat_fwd(Tensor x, Tensor plan, int B, int n_per_sample, float[] dx, float[] bx, int[] nx) -> Tensor')
 _L.define('bev_splat_bwd(Tensor grad, Tensor plan, int B, int n_per_sample, int C, float[] dx, float[] bx, int[] nx) -> Tensor')
+_L.define('mppi_perturb(Tensor nominal, Tensor noise, float[] sigma, float[] lo, float[] hi, bool keep_nominal) -> Tensor')
+_L.define('path_costs(Tensor cost_rows, Tensor? force_cost, Tensor x_last, Tensor goal, float[] weights) -> (Tensor, Tensor)')
+_L.define('mppi_update(Tensor costs, Tensor controls, Tensor nominal, float lam) -> (Tensor, Tensor, Tensor, Tensor)')
 
 
 def _sfx(dtype):
@@ -304,6 +316,103 @@ def _splat_fwd_fake(x, plan, B, n_per_sample, dx, bx, nx):
 @torch.library.register_fake('monoforce::bev_splat_bwd', lib=_L)
 def _splat_bwd_fake(grad, plan, B, n_per_sample, Cc, dx, bx, nx):
     return grad.new_empty(B * n_per_sample, Cc)
+
+
+# ---- MPPI iteration ------------------------------------------------------------------------------------------------------------
+def _mppi_desc(B, T, sigma=(0., 0.), lo=(0., 0.), hi=(0., 0.), weights=(0., 0., 0.), lam=1.0, keep_nominal=False):
+    f2 = lambda v: (C.c_float * 2)(float(v[0]), float(v[1]))  # noqa: E731
+    return _lib.MfMppiDesc(B=int(B), T=int(T), keep_nominal=int(bool(keep_nominal)), sigma=f2(sigma), lo=f2(lo), hi=f2(hi),
+                           w_incl=float(weights[0]), w_force=float(weights[1]), w_goal=float(weights[2]), lam=float(lam))
+
+
+def _f32(t, name):
+    _lib.require_hip_tensor(t, name)
+    if t.dtype != torch.float32:
+        raise TypeError(f'monoforce MPPI ops compute in float32, {name} is {t.dtype}')
+    return t
+
+
+@torch.library.impl(_L, 'mppi_perturb', 'CUDA')
+def _mppi_perturb(nominal, noise, sigma, lo, hi, keep_nominal):
+    nom, nz = _f32(nominal, 'nominal').contiguous(), _f32(noise, 'noise').contiguous()
+    assert nz.dim() == 3 and nz.shape[2] == 2 and tuple(nom.shape) == (nz.shape[1], 2), \
+        f'noise must be [B,T,2] and nominal [T,2], got {tuple(nz.shape)} and {tuple(nom.shape)}'
+    d = _mppi_desc(nz.shape[0], nz.shape[1], sigma=sigma, lo=lo, hi=hi, keep_nominal=keep_nominal)
+    controls = torch.empty_like(nz)
+    with torch.cuda.device(nz.device), _timing.timed('mppi_perturb_kernel', nz.device):
+        _lib.check(_lib.lib().mf_mppi_perturb_f32(C.byref(d), _lib.ptr(nom), _lib.ptr(nz), _lib.ptr(controls), _stream(nz.device)), 'mf_mppi_perturb')
+    return controls
+
+
+@torch.library.impl(_L, 'path_costs', 'CUDA')
+def _path_costs(cost_rows, force_cost, x_last, goal, weights):
+    rows = _f32(cost_rows, 'cost_rows')
+    assert rows.dim() == 3 and rows.shape[2] == 4, f'cost_rows must be [B,T,4], got {tuple(rows.shape)}'
+    B, T = rows.shape[:2]
+    if rows.stride(2) != 1:
+        rows = rows.contiguous()
+    xl = _f32(x_last, 'x_last')
+    assert xl.dim() == 2 and xl.shape[0] == B and xl.shape[1] >= 2, f'x_last must be [B,>=2], got {tuple(xl.shape)}'
+    if xl.stride(1) != 1:
+        xl = xl.contiguous()
+    g = _f32(goal, 'goal').contiguous()
+    assert g.numel() == 2, 'goal must hold (x, y)'
+    assert len(weights) == 3, 'weights = (inclination, force, goal)'
+    fc = None if force_cost is None else _f32(force_cost, 'force_cost').contiguous()
+    assert fc is None or fc.numel() == B, 'force_cost must be [B]'
+    d = _mppi_desc(B, T, weights=weights)
+    d.row_stride_b, d.row_stride_t, d.x_stride_b = rows.stride(0), rows.stride(1), xl.stride(0)
+    costs, terms = torch.empty(B, dtype=torch.float32, device=rows.device), torch.empty(B, 3, dtype=torch.float32, device=rows.device)
+    with torch.cuda.device(rows.device), _timing.timed('path_costs_kernel', rows.device):
+        _lib.check(_lib.lib().mf_path_costs_f32(C.byref(d), _lib.ptr(rows), _lib.ptr(fc), _lib.ptr(xl), _lib.ptr(g), _lib.ptr(costs), _lib.ptr(terms),
+                                                _stream(rows.device)), 'mf_path_costs')
+    return costs, terms
+
+
+def mppi_update_into(costs, controls, nominal, lam, out):
+    """`torch.ops.monoforce.mppi_update` writing the new nominal into `out` [T,2] (which may be `nominal` itself: the planner's resident buffer);
+    returns (out, weights, best, n_valid)."""
+    c, u, nom = _f32(costs, 'costs').contiguous(), _f32(controls, 'controls').contiguous(), _f32(nominal, 'nominal')
+    assert u.dim() == 3 and u.shape[2] == 2 and c.shape == (u.shape[0],) and tuple(nom.shape) == (u.shape[1], 2), \
+        f'costs [B], controls [B,T,2], nominal [T,2] expected, got {tuple(c.shape)}, {tuple(u.shape)}, {tuple(nom.shape)}'
+    assert nom.is_contiguous() and out.is_contiguous() and out.shape == nom.shape and out.dtype == torch.float32 and out.device == u.device
+    B, T = u.shape[:2]
+    dev = u.device
+    d = _mppi_desc(B, T, lam=lam)
+    nbytes = int(_lib.lib().mf_mppi_scratch_bytes(C.byref(d)))
+    if nbytes < 0:
+        raise RuntimeError('mf_mppi_scratch_bytes: ' + _lib.lib().mf_last_error().decode())
+    scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    weights = torch.empty(B, dtype=torch.float32, device=dev)
+    flags = torch.empty(2, dtype=torch.int32, device=dev)
+    best, n_valid = flags[:1], flags[1:]
+    with torch.cuda.device(dev), _timing.timed('mppi_update_kernel', dev):
+        _lib.check(_lib.lib().mf_mppi_update_f32(C.byref(d), _lib.ptr(c), _lib.ptr(u), _lib.ptr(nom), _lib.ptr(weights), _lib.ptr(out), _lib.ptr(best),
+                                                 _lib.ptr(n_valid), _lib.ptr(scratch), C.c_longlong(nbytes), _stream(dev)), 'mf_mppi_update')
+    return out, weights, best, n_valid
+
+
+@torch.library.impl(_L, 'mppi_update', 'CUDA')
+def _mppi_update(costs, controls, nominal, lam):
+    nom = _f32(nominal, 'nominal').contiguous()
+    return mppi_update_into(costs, controls, nom, lam, torch.empty_like(nom))
+
+
+@torch.library.register_fake('monoforce::mppi_perturb', lib=_L)
+def _mppi_perturb_fake(nominal, noise, sigma, lo, hi, keep_nominal):
+    return noise.new_empty(noise.shape)
+
+
+@torch.library.register_fake('monoforce::path_costs', lib=_L)
+def _path_costs_fake(cost_rows, force_cost, x_last, goal, weights):
+    B = cost_rows.shape[0]
+    return cost_rows.new_empty(B), cost_rows.new_empty(B, 3)
+
+
+@torch.library.register_fake('monoforce::mppi_update', lib=_L)
+def _mppi_update_fake(costs, controls, nominal, lam):
+    B = controls.shape[0]
+    return (nominal.new_empty(nominal.shape), costs.new_empty(B), costs.new_empty(1, dtype=torch.int32), costs.new_empty(1, dtype=torch.int32))
 
 
 # ---- functional entries ------------------------------------------------------------------------------------------------------
