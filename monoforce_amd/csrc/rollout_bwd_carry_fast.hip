@@ -3,7 +3,7 @@
 #include "rollout_bwd_kernel.h"
 
 namespace mf {
-int launch_rollout_bwd_carry_fast_f32(const RolloutBwdArgs<float>& a, LaneMap m, int integ, int block, hipStream_t st) {
-  return launch_rollout_bwd<float, true, false, true>(a, m, integ, block, st);
+int launch_rollout_bwd_carry_fast_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st) {
+  return launch_rollout_bwd<float, true, false, true>(a, r, integ, st);
 }
 }  // namespace mf

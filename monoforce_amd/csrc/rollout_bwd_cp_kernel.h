@@ -35,7 +35,7 @@ namespace mf {
 // Also tried and not kept -- a three-stage single-wave pipeline (gathers of step n - 2, the rest of the recompute of step n - 1
 // BESIDE the chain of step n, three register sets, unrolled by three): the same ~350 instructions per step, interleaved by
 // the compiler instead of run one stream after the other, and slower: 0.399 vs 0.367 ms (dynamics(): 0.548 vs 0.448).
-enum { kCpEarly = 0, kCpLate = 1, kCpSaved = 2, kCpStream = 3 };
+// (MODE: kCpEarly, kCpLate, kCpSaved, kCpStream -- rollout_route.h)
 #ifdef MF_STREAM_PROFILE      // A/B build: where the waves of the streaming backward spend their cycles (tools/stream_profile.py)
 extern __device__ unsigned long long mf_stream_prof[32];
 #define MF_PROF_T(v) const unsigned long long v = __builtin_readcyclecounter()
@@ -1345,87 +1345,48 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
   }
 }
 
-bool use_component_parallel_bwd(const MfRolloutDesc* d, const MfRolloutBwdBufs* p, int scalar_bytes = 4);
-long long cp_record_bytes(const MfRolloutDesc* d, int scalar_bytes);      // bytes of the forward's per-step record for this launch shape (0: none)
-bool cp_loss_fusable(const MfRolloutDesc* d);           // both directions of this launch can carry the fused physics loss
-bool cp_bwd_wants_zmu(const MfRolloutDesc* d, bool has_rec, bool has_mu);      // the launch will run the record-reading kernel on interleaved maps if it gets them
-int launch_rollout_bwd_cp_f32(const RolloutBwdArgs<float>& a, int integ, bool xs_only, hipStream_t st);   // a.gcontrols may be NULL
-int launch_rollout_bwd_cp_dynamics_f32(const RolloutBwdArgs<float>& a, bool xs_only, hipStream_t st);      // rollout_bwd_dyn_cp_fast.hip
-void launch_rollout_bwd_cp_stream_f32(const RolloutBwdArgs<float>& a, bool xs_only, unsigned grid, hipStream_t st);   // rollout_bwd_cp_stream_fast.hip
-void launch_rollout_bwd_cp_stream_dynamics_f32(const RolloutBwdArgs<float>& a, bool xs_only, unsigned grid, hipStream_t st);   // rollout_bwd_dyn_cp_stream_fast.hip
-
-// Largest grid (workgroups = waves of rollouts) the streaming form takes: its LDS ring allows two workgroups per CU with six slots
-// (2 x 60 / 72 KB of the CU's 160 KB), one with twelve; dynamics() carries six more planes per slot (96 / 108 KB with six slots: one
-// workgroup per CU).  MF_CP_STREAM_MAX_GRID overrides the default integrator's limit (A/B runs).
-inline unsigned cp_stream_max_grid(int integ = MF_INTEG_ODEINT_EULER) {
-  static const int env = getenv("MF_CP_STREAM_MAX_GRID") ? atoi(getenv("MF_CP_STREAM_MAX_GRID")) : -1;
-  const unsigned cus = (unsigned)device_cus();
-  const unsigned v = env >= 0 ? (unsigned)env : 2u * cus;      // two workgroups per CU (MI355X: 512); dynamics(): one
-  return integ == MF_INTEG_ODEINT_EULER ? v : (v < cus ? v : cus);
+// One launch of the variant the route calls for (rollout_route.hip: form, ring, interleaved maps, LDS window, fused loss); a.gcontrols may
+// be NULL.  The streaming form's kernels have translation units of their own.
+int launch_rollout_bwd_cp_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st);
+int launch_rollout_bwd_cp_f64(const RolloutBwdArgs<double>& a, const BwdRoute& r, int integ, hipStream_t st);
+int launch_rollout_bwd_cp_dynamics_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, hipStream_t st);      // rollout_bwd_dyn_cp_fast.hip
+void launch_rollout_bwd_cp_stream_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, hipStream_t st);   // rollout_bwd_cp_stream_fast.hip
+void launch_rollout_bwd_cp_stream_dynamics_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, hipStream_t st);   // rollout_bwd_dyn_cp_stream_fast.hip
+void launch_rollout_bwd_cp_stream_f64(const RolloutBwdArgs<double>& a, const BwdRoute& r, hipStream_t st);   // rollout_bwd_cp_f64.hip (the validation build)
+inline void launch_rollout_bwd_cp_stream_any(const RolloutBwdArgs<float>& a, int integ, const BwdRoute& r, hipStream_t st) {
+  if (integ == MF_INTEG_ODEINT_EULER) launch_rollout_bwd_cp_stream_f32(a, r, st); else launch_rollout_bwd_cp_stream_dynamics_f32(a, r, st);
 }
-
-// one launch of the variant (positions-only loss?, control gradient?, late recompute?) the arguments call for
-void launch_rollout_bwd_cp_stream_f64(const RolloutBwdArgs<double>& a, bool xs_only, unsigned grid, hipStream_t st);   // rollout_cp_f64.hip (the validation build)
-int launch_rollout_bwd_cp_f64(const RolloutBwdArgs<double>& a, int integ, bool xs_only, hipStream_t st);
-inline void launch_rollout_bwd_cp_stream_any(const RolloutBwdArgs<float>& a, int integ, bool xs_only, unsigned grid, hipStream_t st) {
-  if (integ == MF_INTEG_ODEINT_EULER) launch_rollout_bwd_cp_stream_f32(a, xs_only, grid, st); else launch_rollout_bwd_cp_stream_dynamics_f32(a, xs_only, grid, st);
-}
-inline void launch_rollout_bwd_cp_stream_any(const RolloutBwdArgs<double>& a, int, bool xs_only, unsigned grid, hipStream_t st) {
-  launch_rollout_bwd_cp_stream_f64(a, xs_only, grid, st);      // (default integrator only: cp_stream_max_grid_of<double>)
-}
-// float64 (validation build): a ring slot is twice the bytes -- six slots of the default integrator's planes fit a CU's LDS (123 / 147 KB,
-// one workgroup per CU), dynamics()' sixteen / eighteen planes do not: its record is read by the computing wave itself (kCpSaved)
-template <typename S>
-inline unsigned cp_stream_max_grid_of(int integ) {
-  if (sizeof(S) == 8) return integ == MF_INTEG_ODEINT_EULER ? cp_stream_max_grid(integ) : 0u;
-  return cp_stream_max_grid(integ);
+inline void launch_rollout_bwd_cp_stream_any(const RolloutBwdArgs<double>& a, int, const BwdRoute& r, hipStream_t st) {
+  launch_rollout_bwd_cp_stream_f64(a, r, st);      // (default integrator only: the route streams no float64 dynamics() record)
 }
 template <typename S, int INTEG>
-int launch_rollout_bwd_cp_variant(const RolloutBwdArgs<S>& a, bool xs_only, hipStream_t st) {
-  const long long threads = (long long)a.B * 16;
-  const unsigned grid = (unsigned)((threads + 63) / 64);      // waves of rollouts
-  const unsigned block = wave_unit_block(grid), wgs = (unsigned)((threads + block - 1) / block);      // (the streaming form: 192 threads, its own)
+int launch_rollout_bwd_cp_variant(const RolloutBwdArgs<S>& a, const BwdRoute& r, hipStream_t st) {
+  const unsigned grid = r.grid, block = r.block;
+  const int mode = r.cp_mode;
   const bool gc = a.gcontrols != nullptr;
-  static const int forced = getenv("MF_CP_BWD_MODE") ? atoi(getenv("MF_CP_BWD_MODE")) : -1;      // A/B (tools/ab_cp.py): 0 early, 1 late, 2 record read by one wave
-  // the forward's record when there is one: a second wave per workgroup streams it through LDS (default integrator, while the
-  // rings fit the CUs' LDS), else one wave reads it itself; without a record at most one wave per SIMD: late recompute
-  const int saved_mode = grid <= cp_stream_max_grid_of<S>(INTEG) && forced != kCpSaved ? kCpStream : kCpSaved;
-  const int mode = a.rec ? saved_mode : (forced >= 0 && forced < kCpSaved ? forced : ((long long)grid <= device_simds() ? kCpLate : kCpEarly));
-#define MF_BCP(XS_, GC_, M_) MF_KLAUNCH((rollout_bwd_cp_kernel<S, INTEG, XS_, GC_, M_>), dim3(wgs), dim3(block), 0, st, a)
-  // (the record-reading mode on the interleaved maps the host staged: cp_bwd_wants_zmu)
+#define MF_BCP(XS_, GC_, M_) MF_KLAUNCH((rollout_bwd_cp_kernel<S, INTEG, XS_, GC_, M_>), dim3(grid), dim3(block), 0, st, a)
+  // (the record-reading mode on the interleaved maps the host staged)
   constexpr bool kZmu = std::is_same<S, float>::value && INTEG == MF_INTEG_ODEINT_EULER;
-  // (measured and dropped, round 5: the LDS gradient window in this record-reading form -- 3072 / 4096 rollouts: 0.382 / 0.406 ms with or without)
-#define MF_BCP_Z(XS_, GC_) do { if constexpr (kZmu) { if (a.zmu) { MF_KLAUNCH((rollout_bwd_cp_kernel<S, INTEG, XS_, GC_, kCpSaved, 6, 3, kZmu>), dim3(wgs), dim3(block), 0, st, a); break; } } MF_BCP(XS_, GC_, kCpSaved); } while (0)
-  // early recompute beyond one wave per SIMD on ONE shared power-of-two map pair: the cell writes through an LDS window per workgroup of
-  // eight waves (one workgroup per CU: 128 KB); every workgroup must be full (no early exit in front of its barriers).  MF_BWD_WIN=0: A/B.
-  static const bool win_off = getenv("MF_BWD_WIN") && atoi(getenv("MF_BWD_WIN")) == 0;
+#define MF_BCP_Z(XS_, GC_) do { if constexpr (kZmu) { if (r.zmu) { MF_KLAUNCH((rollout_bwd_cp_kernel<S, INTEG, XS_, GC_, kCpSaved, 6, 3, kZmu>), dim3(grid), dim3(block), 0, st, a); break; } } MF_BCP(XS_, GC_, kCpSaved); } while (0)
+  // (early recompute with the cell writes through an LDS window per workgroup of eight waves)
   constexpr bool kWin = std::is_same<S, float>::value;
-  const bool win = kWin && !win_off && mode == kCpEarly && a.map_shared && a.H == a.W && (a.H & (a.H - 1)) == 0 && threads % 512 == 0;
-#define MF_BCP_W(XS_, GC_) do { if constexpr (kWin) { if (win) { MF_KLAUNCH((rollout_bwd_cp_kernel<S, INTEG, XS_, GC_, kCpEarly, 6, 3, false, kWin>), dim3((unsigned)(threads / 512)), dim3(512), 0, st, a); break; } } MF_BCP(XS_, GC_, kCpEarly); } while (0)
-#define MF_BCP_L(XS_, GC_) do { if (mode == kCpStream) launch_rollout_bwd_cp_stream_any(a, INTEG, xs_only, grid, st); else if (mode == kCpSaved) MF_BCP_Z(XS_, GC_); else if (mode == kCpLate) MF_BCP(XS_, GC_, kCpLate); else MF_BCP_W(XS_, GC_); } while (0)
-  // ONE1: the fused physics loss of the one-wave forms (float32; a.loss_gt set by the host for such a launch) -- instantiations of their own
+#define MF_BCP_W(XS_, GC_) do { if constexpr (kWin) { if (r.win) { MF_KLAUNCH((rollout_bwd_cp_kernel<S, INTEG, XS_, GC_, kCpEarly, 6, 3, false, kWin>), dim3(grid), dim3(block), 0, st, a); break; } } MF_BCP(XS_, GC_, kCpEarly); } while (0)
+#define MF_BCP_L(XS_, GC_) do { if (mode == kCpStream) launch_rollout_bwd_cp_stream_any(a, INTEG, r, st); else if (mode == kCpSaved) MF_BCP_Z(XS_, GC_); else if (mode == kCpLate) MF_BCP(XS_, GC_, kCpLate); else MF_BCP_W(XS_, GC_); } while (0)
+  // ONE1: the fused physics loss of the early-recompute form (float32; a.loss_gt set by the host for such a launch) -- instantiations of their own
   bool one1_done = false;
   if constexpr (std::is_same<S, float>::value) {
-    if (xs_only && a.loss_gt != nullptr && mode != kCpStream) {
-      // (the early-recompute form only -- more than one wave per SIMD: in the record-reading and the late-recompute forms the kernel loses what
-      //  the loss's own two small launches cost, profiles/r6_ab_one_wave_loss.txt; cp_loss_one_wave in rollout_bwd.hip offers the fusion to
-      //  exactly the shapes that run early recompute)
-      MF_REQUIRE(mode == kCpEarly, MF_ERR_UNSUPPORTED, "rollout_bwd: only the early-recompute one-wave form carries a fused loss");
+    if (r.one1) {
       one1_done = true;
-#define MF_BCP1(GC_, M_, Z_, W_, G_, B_) MF_KLAUNCH((rollout_bwd_cp_kernel<S, INTEG, true, GC_, M_, 6, 3, Z_, W_, true>), dim3(G_), dim3(B_), 0, st, a)
-#define MF_BCP1_L(GC_) do {                                                                                                   \
-        if (win) MF_BCP1(GC_, kCpEarly, false, kWin, (unsigned)(threads / 512), 512);                                    \
-        else MF_BCP1(GC_, kCpEarly, false, false, wgs, block);                                                                \
-      } while (0)
+#define MF_BCP1(GC_, W_) MF_KLAUNCH((rollout_bwd_cp_kernel<S, INTEG, true, GC_, kCpEarly, 6, 3, false, W_, true>), dim3(grid), dim3(block), 0, st, a)
+#define MF_BCP1_L(GC_) do { if (r.win) MF_BCP1(GC_, kWin); else MF_BCP1(GC_, false); } while (0)
       if (gc) MF_BCP1_L(true); else MF_BCP1_L(false);
 #undef MF_BCP1_L
 #undef MF_BCP1
     }
   }
   if (!one1_done) {
-    MF_REQUIRE(a.loss_gt == nullptr || mode == kCpStream, MF_ERR_UNSUPPORTED, "rollout_bwd: the one-wave fused physics loss exists for float32 positions-only launches");
-    if (xs_only) { if (gc) MF_BCP_L(true, true); else MF_BCP_L(true, false); }
-    else         { if (gc) MF_BCP_L(false, true); else MF_BCP_L(false, false); }
+    if (r.xs_only) { if (gc) MF_BCP_L(true, true); else MF_BCP_L(true, false); }
+    else           { if (gc) MF_BCP_L(false, true); else MF_BCP_L(false, false); }
   }
 #undef MF_BCP_L
 #undef MF_BCP_W

@@ -13,16 +13,14 @@ extern "C" int mf_debug_stream_profile(unsigned long long* out32, int reset) {
 #endif
 namespace mf {
 
-// Workgroup = the computing wave + two fetching waves.  Ring: twelve slots while a CU holds one workgroup (B <= 1024: 120 / 144 KB
-// of its 160 KB LDS -- the fetching waves run up to four batches ahead), six for two workgroups per CU (60 / 72 KB each; the
-// positions-only variants, held to 256 registers there, fetch in batches of TWO steps: no scratch).
-void launch_rollout_bwd_cp_stream_f32(const RolloutBwdArgs<float>& a, bool xs_only, unsigned grid, hipStream_t st) {
+// Workgroup = the computing wave + two fetching waves.  Ring: twelve slots or six (rollout_route.hip; the positions-only variants of the
+// six-slot form, held to 256 registers there, fetch in batches of TWO steps: no scratch).
+void launch_rollout_bwd_cp_stream_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, hipStream_t st) {
   constexpr int I = MF_INTEG_ODEINT_EULER;
-  const bool gc = a.gcontrols != nullptr;
-  static const int big_ring_env = getenv("MF_CP_STREAM_BIG_RING_MAX_GRID") ? atoi(getenv("MF_CP_STREAM_BIG_RING_MAX_GRID")) : -1;
-  const unsigned big_ring_max = big_ring_env >= 0 ? (unsigned)big_ring_env : (unsigned)device_cus();      // one workgroup per CU
-#define MF_BCPS(XS_, GC_) do { if (grid <= big_ring_max) MF_KLAUNCH((rollout_bwd_cp_kernel<float, I, XS_, GC_, kCpStream, 12>), dim3(grid), dim3(192), 0, st, a); \
-                               else MF_KLAUNCH((rollout_bwd_cp_kernel<float, I, XS_, GC_, kCpStream, 6, (XS_ ? 2 : 3)>), dim3(grid), dim3(192), 0, st, a); } while (0)
+  const bool gc = a.gcontrols != nullptr, xs_only = r.xs_only;
+  const unsigned grid = r.grid;
+#define MF_BCPS(XS_, GC_) do { if (r.ring_slots == 12) MF_KLAUNCH((rollout_bwd_cp_kernel<float, I, XS_, GC_, kCpStream, 12>), dim3(grid), dim3(r.block), 0, st, a); \
+                               else MF_KLAUNCH((rollout_bwd_cp_kernel<float, I, XS_, GC_, kCpStream, 6, (XS_ ? 2 : 3)>), dim3(grid), dim3(r.block), 0, st, a); } while (0)
   if (xs_only) { if (gc) MF_BCPS(true, true); else MF_BCPS(true, false); }
   else         { if (gc) MF_BCPS(false, true); else MF_BCPS(false, false); }
 #undef MF_BCPS

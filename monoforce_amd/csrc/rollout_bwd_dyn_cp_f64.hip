@@ -5,8 +5,8 @@
 
 namespace mf {
 
-int launch_rollout_bwd_cp_dynamics_f64(const RolloutBwdArgs<double>& a, bool xs_only, hipStream_t st) {
-  return launch_rollout_bwd_cp_variant<double, MF_INTEG_DYNAMICS>(a, xs_only, st);
+int launch_rollout_bwd_cp_dynamics_f64(const RolloutBwdArgs<double>& a, const BwdRoute& r, hipStream_t st) {
+  return launch_rollout_bwd_cp_variant<double, MF_INTEG_DYNAMICS>(a, r, st);
 }
 
 }  // namespace mf

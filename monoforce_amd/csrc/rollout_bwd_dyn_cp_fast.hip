@@ -4,8 +4,8 @@
 
 namespace mf {
 
-int launch_rollout_bwd_cp_dynamics_f32(const RolloutBwdArgs<float>& a, bool xs_only, hipStream_t st) {
-  return launch_rollout_bwd_cp_variant<float, MF_INTEG_DYNAMICS>(a, xs_only, st);
+int launch_rollout_bwd_cp_dynamics_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, hipStream_t st) {
+  return launch_rollout_bwd_cp_variant<float, MF_INTEG_DYNAMICS>(a, r, st);
 }
 
 }  // namespace mf

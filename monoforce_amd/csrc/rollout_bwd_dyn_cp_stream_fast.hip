@@ -6,10 +6,10 @@
 namespace mf {
 
 // six-slot ring (96 / 108 KB of LDS: one workgroup per CU, B <= 1024)
-void launch_rollout_bwd_cp_stream_dynamics_f32(const RolloutBwdArgs<float>& a, bool xs_only, unsigned grid, hipStream_t st) {
+void launch_rollout_bwd_cp_stream_dynamics_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, hipStream_t st) {
   constexpr int I = MF_INTEG_DYNAMICS;
-  const bool gc = a.gcontrols != nullptr;
-#define MF_BCPS(XS_, GC_) MF_KLAUNCH((rollout_bwd_cp_kernel<float, I, XS_, GC_, kCpStream, 6>), dim3(grid), dim3(192), 0, st, a)
+  const bool gc = a.gcontrols != nullptr, xs_only = r.xs_only;
+#define MF_BCPS(XS_, GC_) MF_KLAUNCH((rollout_bwd_cp_kernel<float, I, XS_, GC_, kCpStream, 6>), dim3(r.grid), dim3(r.block), 0, st, a)
   if (xs_only) { if (gc) MF_BCPS(true, true); else MF_BCPS(true, false); }
   else         { if (gc) MF_BCPS(false, true); else MF_BCPS(false, false); }
 #undef MF_BCPS

@@ -3,10 +3,10 @@
 #include "rollout_bwd_kernel.h"
 
 namespace mf {
-int launch_rollout_bwd_joints_f32(const RolloutBwdArgs<float>& a, LaneMap m, int integ, int block, hipStream_t st) {
-  return launch_rollout_bwd<float, false, true>(a, m, integ, block, st);
+int launch_rollout_bwd_joints_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st) {
+  return launch_rollout_bwd<float, false, true>(a, r, integ, st);
 }
-int launch_rollout_bwd_joints_f64(const RolloutBwdArgs<double>& a, LaneMap m, int integ, int block, hipStream_t st) {
-  return launch_rollout_bwd<double, false, true>(a, m, integ, block, st);
+int launch_rollout_bwd_joints_f64(const RolloutBwdArgs<double>& a, const BwdRoute& r, int integ, hipStream_t st) {
+  return launch_rollout_bwd<double, false, true>(a, r, integ, st);
 }
 }  // namespace mf

@@ -11,7 +11,7 @@
 // constants (queries influence samples only through the fractions); |v| has zero gradient at v = 0;
 // x / clamp(|x|, eps) differentiates through |x| only when |x| >= eps.
 #pragma once
-#include "rollout_fwd_kernel.h"   // Mth<>, locate_m<>, LaneMap
+#include "rollout_fwd_kernel.h"   // Mth<>, locate_m<>; rollout_route.h: LaneMap, BwdRoute
 
 namespace mf {
 
@@ -1020,10 +1020,9 @@ __global__ void __launch_bounds__(WIN ? 512 : (G > 256 ? G : 256)) rollout_bwd_k
 }
 
 template <typename S, bool FAST, bool JOINTS = false, bool CARRY = true>
-int launch_rollout_bwd(const RolloutBwdArgs<S>& a, LaneMap m, int integ, int block, hipStream_t st) {
-  if (m.G > 64) block = m.G;   // a rollout spread over several waves: exactly one rollout per workgroup (LDS + barrier)
-  const long long threads = (long long)a.B * m.G;
-  const unsigned grid = (unsigned)((threads + block - 1) / block);
+int launch_rollout_bwd(const RolloutBwdArgs<S>& a, const BwdRoute& r, int integ, hipStream_t st) {
+  const LaneMap m = r.m;
+  const unsigned grid = r.grid, block = r.block;
   bool launched = false;
 #define MF_CASE(G_, P_)                                                                                                           \
   if (!launched && m.G == G_ && m.PPL == P_) {                                                                                     \
@@ -1048,9 +1047,9 @@ int launch_rollout_bwd(const RolloutBwdArgs<S>& a, LaneMap m, int integ, int blo
 // the positions-only (XS_ONLY) instantiations with accumulator carry-over, one point per lane inside a wave (G = 4 .. 64), plain or
 // interleaved maps: the saturated launches of small bodies (rollout_bwd_xs_fast.hip)
 template <typename S, bool ZMU, bool WIN = false, bool CARRY = true, bool LOSS = false>
-int launch_rollout_bwd_xs(const RolloutBwdArgs<S>& a, LaneMap m, int integ, int block, hipStream_t st) {
-  const long long threads = (long long)a.B * m.G;
-  const unsigned grid = (unsigned)((threads + block - 1) / block);
+int launch_rollout_bwd_xs(const RolloutBwdArgs<S>& a, const BwdRoute& r, int integ, hipStream_t st) {
+  const LaneMap m = r.m;
+  const unsigned grid = r.grid, block = r.block;
   bool launched = false;
 #define MF_CASE(G_)                                                                                                                              \
   if (!launched && m.G == G_ && m.PPL == 1) {                                                                                                     \
@@ -1071,9 +1070,9 @@ int launch_rollout_bwd_xs(const RolloutBwdArgs<S>& a, LaneMap m, int integ, int 
 // ... and for one rollout per wave with 2 / 4 / 8 points per lane (bodies of 65 .. 512 points beyond the record-reading multi-wave range):
 // a positions-only upstream compiles out 6 PPL row loads and the impulse adjoints per lane and step (rollout_bwd_xs_ppl_fast.hip; round 6)
 template <typename S>
-int launch_rollout_bwd_xs_ppl(const RolloutBwdArgs<S>& a, LaneMap m, int integ, int block, hipStream_t st) {
-  const long long threads = (long long)a.B * m.G;
-  const unsigned grid = (unsigned)((threads + block - 1) / block);
+int launch_rollout_bwd_xs_ppl(const RolloutBwdArgs<S>& a, const BwdRoute& r, int integ, hipStream_t st) {
+  const LaneMap m = r.m;
+  const unsigned grid = r.grid, block = r.block;
   bool launched = false;
 #define MF_CASE(P_)                                                                                                                              \
   if (!launched && m.G == 64 && m.PPL == P_) {                                                                                                    \
@@ -1090,20 +1089,19 @@ int launch_rollout_bwd_xs_ppl(const RolloutBwdArgs<S>& a, LaneMap m, int integ, 
   MF_REQUIRE(e == hipSuccess, MF_ERR_LAUNCH, std::string("rollout_bwd (positions only, several points per lane) launch: ") + hipGetErrorString(e));
   return MF_OK;
 }
-int launch_rollout_bwd_xs_ppl_fast_f32(const RolloutBwdArgs<float>& a, LaneMap m, int integ, int block, hipStream_t st);      // rollout_bwd_xs_ppl_fast.hip
-int launch_rollout_bwd_xs_fast_f32(const RolloutBwdArgs<float>& a, LaneMap m, int integ, int block, bool zmu, hipStream_t st);      // rollout_bwd_xs_fast.hip
-int launch_rollout_bwd_xs_win_fast_f32(const RolloutBwdArgs<float>& a, LaneMap m, int integ, int block, bool zmu, bool carry, hipStream_t st);  // rollout_bwd_xs_win_fast.hip
+// the float32 fast-math instantiations, one translation unit each
+int launch_rollout_bwd_xs_ppl_fast_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st);      // rollout_bwd_xs_ppl_fast.hip
+int launch_rollout_bwd_xs_fast_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st);          // rollout_bwd_xs_fast.hip
+int launch_rollout_bwd_xs_win_fast_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st);      // rollout_bwd_xs_win_fast.hip
 // ... the same with the fused physics loss (LOSS; a.loss_gt set): rollout_bwd_xs_loss_fast.hip, rollout_bwd_xs_win_loss_fast.hip
-int launch_rollout_bwd_xs_loss_fast_f32(const RolloutBwdArgs<float>& a, LaneMap m, int integ, int block, bool zmu, hipStream_t st);
-int launch_rollout_bwd_xs_win_loss_fast_f32(const RolloutBwdArgs<float>& a, LaneMap m, int integ, int block, bool zmu, bool carry, hipStream_t st);
-
-// defined in rollout_bwd_fast.hip (plain flush) and rollout_bwd_carry_fast.hip (accumulator carry-over)
-int launch_rollout_bwd_fast_f32(const RolloutBwdArgs<float>& a, LaneMap m, int integ, int block, hipStream_t st);
-int launch_rollout_bwd_carry_fast_f32(const RolloutBwdArgs<float>& a, LaneMap m, int integ, int block, hipStream_t st);
-// defined in rollout_bwd_joints.hip (exact arithmetic, like the articulated forward)
-int launch_rollout_bwd_joints_f32(const RolloutBwdArgs<float>& a, LaneMap m, int integ, int block, hipStream_t st);
-int launch_rollout_bwd_joints_f64(const RolloutBwdArgs<double>& a, LaneMap m, int integ, int block, hipStream_t st);
-// defined in rollout_bwd_joints_fast.hip
-int launch_rollout_bwd_joints_fast_f32(const RolloutBwdArgs<float>& a, LaneMap m, int integ, int block, hipStream_t st);
+int launch_rollout_bwd_xs_loss_fast_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st);
+int launch_rollout_bwd_xs_win_loss_fast_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st);
+// rollout_bwd_fast.hip (plain flush) and rollout_bwd_carry_fast.hip (accumulator carry-over)
+int launch_rollout_bwd_fast_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st);
+int launch_rollout_bwd_carry_fast_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st);
+// rollout_bwd_joints.hip (exact arithmetic, like the articulated forward) and rollout_bwd_joints_fast.hip
+int launch_rollout_bwd_joints_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st);
+int launch_rollout_bwd_joints_f64(const RolloutBwdArgs<double>& a, const BwdRoute& r, int integ, hipStream_t st);
+int launch_rollout_bwd_joints_fast_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st);
 
 }  // namespace mf

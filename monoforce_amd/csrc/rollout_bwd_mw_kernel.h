@@ -659,33 +659,23 @@ __global__ void __launch_bounds__(G > 64 ? G : 64) rollout_bwd_mw_kernel(const R
   }
 }
 
-// defined in rollout_bwd_mw_fast.hip
-bool use_multiwave_bwd(const MfRolloutDesc* d, const MfRolloutBwdBufs* p);   // this backward goes to the kernels above
-long long mw_record_bytes(const MfRolloutDesc* d, int scalar_bytes = 4);      // bytes of the record the forward keeps for them (0: none)
-int launch_rollout_bwd_mw_f32(const RolloutBwdArgs<float>& a, int G, int integ, bool xs_only, hipStream_t st);
-int launch_rollout_bwd_mw_f64(const RolloutBwdArgs<double>& a, int G, int integ, bool xs_only, hipStream_t st);      // rollout_mw_f64.hip
-// cells per side of a rollout's LDS gradient tile; 0 = none.  Measured (B = 64 x N = 223: 1.094 -> 1.038 ms; 256 x 64: 0.861 -> 0.845;
-// 1024 x 32: 0.971 -> 0.967; 256 x 16: 0.692 -> 0.883 -- four tiles per wave collide in the LDS): whole-wave groups only
-constexpr int mw_tile_edge(int G) { return G >= 64 ? 64 : 0; }
+int launch_rollout_bwd_mw_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st);       // rollout_bwd_mw_fast.hip
+int launch_rollout_bwd_mw_f64(const RolloutBwdArgs<double>& a, const BwdRoute& r, int integ, hipStream_t st);      // rollout_mw_f64.hip
+constexpr int kMwTileEdge = 64;      // cells per side of a rollout's LDS gradient tile (whole-wave groups only: rollout_route.hip)
 
-// one launch of the instantiation the arguments call for (S = float: rollout_bwd_mw_fast.hip; S = double: rollout_mw_f64.hip)
+// one launch of the instantiation the route calls for (S = float: rollout_bwd_mw_fast.hip; S = double: rollout_mw_f64.hip)
 template <typename S>
-int launch_rollout_bwd_mw_t(const RolloutBwdArgs<S>& a, int G, int integ, bool xs_only, hipStream_t st) {
-  // LDS gradient tiles (rollout_bwd_mw_kernel.h) while every workgroup of the launch is resident with its tiles: 160 KB per CU,
-  // 256 CUs.  MF_MW_TILE=0 keeps the register accumulators (A/B runs, parity of the two routes).
-  static const bool tile_off = getenv("MF_MW_TILE") && atoi(getenv("MF_MW_TILE")) == 0;
+int launch_rollout_bwd_mw_t(const RolloutBwdArgs<S>& a, const BwdRoute& r, int integ, hipStream_t st) {
+  const int G = r.m.G;
+  const unsigned grid = r.grid, blk = r.block;
+  const bool xs_only = r.xs_only, dyn = integ == MF_INTEG_DYNAMICS;
   bool launched = false;
 #define MF_LAUNCH(G_, XS_, T_, I_) MF_KLAUNCH((rollout_bwd_mw_kernel<S, G_, XS_, T_, I_>), dim3(grid), dim3(blk), 0, st, a)
 #define MF_CASE(G_)                                                                                              \
   if (!launched && G == G_) {                                                                                    \
     launched = true;                                                                                             \
-    constexpr int blk = G_ > 64 ? G_ : 64;                                                                       \
-    constexpr int TE = mw_tile_edge(G_);                                                                         \
-    constexpr long long lds = (long long)(G_ > 64 ? 1 : 64 / G_) * 2 * (TE + 1) * TE * (long long)sizeof(S) + 4096;                       \
-    const unsigned grid = (unsigned)(((long long)a.B * G_ + blk - 1) / blk);                                     \
-    const bool tile = TE > 0 && !tile_off && (long long)((grid + (unsigned)device_cus() - 1) / (unsigned)device_cus()) * lds <= 160 * 1024 && (long long)a.H * a.W < (1ll << 30); \
-    const bool dyn = integ == MF_INTEG_DYNAMICS;                                                                 \
-    if (tile) {                                                                                                  \
+    constexpr int TE = G_ >= 64 ? kMwTileEdge : 0;      /* (the tiled instantiations that exist) */               \
+    if (r.tile) {                                                                                                \
       if constexpr (TE > 0) {                                                                                    \
         if (dyn) { if (xs_only) MF_LAUNCH(G_, true, TE, MF_INTEG_DYNAMICS); else MF_LAUNCH(G_, false, TE, MF_INTEG_DYNAMICS); }          \
         else     { if (xs_only) MF_LAUNCH(G_, true, TE, MF_INTEG_ODEINT_EULER); else MF_LAUNCH(G_, false, TE, MF_INTEG_ODEINT_EULER); }  \

@@ -4,7 +4,7 @@
 #include "rollout_bwd_kernel.h"
 
 namespace mf {
-int launch_rollout_bwd_xs_fast_f32(const RolloutBwdArgs<float>& a, LaneMap m, int integ, int block, bool zmu, hipStream_t st) {
-  return zmu ? launch_rollout_bwd_xs<float, true>(a, m, integ, block, st) : launch_rollout_bwd_xs<float, false>(a, m, integ, block, st);
+int launch_rollout_bwd_xs_fast_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st) {
+  return r.zmu ? launch_rollout_bwd_xs<float, true>(a, r, integ, st) : launch_rollout_bwd_xs<float, false>(a, r, integ, st);
 }
 }  // namespace mf

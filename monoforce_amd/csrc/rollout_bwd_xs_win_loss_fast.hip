@@ -3,8 +3,8 @@
 #include "rollout_bwd_kernel.h"
 
 namespace mf {
-int launch_rollout_bwd_xs_win_loss_fast_f32(const RolloutBwdArgs<float>& a, LaneMap m, int integ, int block, bool zmu, bool carry, hipStream_t st) {
-  if (carry) return zmu ? launch_rollout_bwd_xs<float, true, true, true, true>(a, m, integ, block, st) : launch_rollout_bwd_xs<float, false, true, true, true>(a, m, integ, block, st);
-  return zmu ? launch_rollout_bwd_xs<float, true, true, false, true>(a, m, integ, block, st) : launch_rollout_bwd_xs<float, false, true, false, true>(a, m, integ, block, st);
+int launch_rollout_bwd_xs_win_loss_fast_f32(const RolloutBwdArgs<float>& a, const BwdRoute& r, int integ, hipStream_t st) {
+  if (r.carry) return r.zmu ? launch_rollout_bwd_xs<float, true, true, true, true>(a, r, integ, st) : launch_rollout_bwd_xs<float, false, true, true, true>(a, r, integ, st);
+  return r.zmu ? launch_rollout_bwd_xs<float, true, true, false, true>(a, r, integ, st) : launch_rollout_bwd_xs<float, false, true, false, true>(a, r, integ, st);
 }
 }  // namespace mf

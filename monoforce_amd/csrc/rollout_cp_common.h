@@ -201,4 +201,9 @@ __device__ __forceinline__ void bstore3(Rsrc r, unsigned voff, unsigned soff, S 
 }
 
 }  // namespace cp
+
+// (z, mu) of ONE shared map pair interleaved cell by cell, for the kernels that gather both (ZMU): the caller's staged pair, else its
+// scratch, filled by one pass in front of the launch (rollout_fwd.hip; without a friction map the second component is 1)
+template <typename S>
+const S* interleaved_maps(const void* staged, void* scratch, const S* z, const S* mu, int n, hipStream_t st);
 }  // namespace mf

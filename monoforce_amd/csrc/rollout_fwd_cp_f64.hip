@@ -7,8 +7,8 @@
 
 namespace mf {
 
-int launch_rollout_fwd_cp_f64(const RolloutArgs<double>& a, int integ, bool forces, bool zmu, hipStream_t st) {
-  return launch_rollout_fwd_cp_t<double>(a, integ, forces, zmu, st);
+int launch_rollout_fwd_cp_f64(const RolloutArgs<double>& a, const FwdRoute& r, int integ, hipStream_t st) {
+  return launch_rollout_fwd_cp_t<double>(a, r, integ, st);
 }
 
 }  // namespace mf

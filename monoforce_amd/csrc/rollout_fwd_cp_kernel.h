@@ -366,26 +366,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
   }
 }
 
-// true when the component-parallel kernels cover this launch: float32 fast math, a rigid body of <= 4 points, full outputs
-// (or states only), and few enough rollouts that the launch is bound by the instruction stream of its waves
-bool use_component_parallel(const MfRolloutDesc* d, const MfRolloutFwdBufs* p, int scalar_bytes = 4);      // (8: the float64 validation build)
-int launch_rollout_fwd_cp_f32(const RolloutArgs<float>& a, int integ, bool forces, bool zmu, hipStream_t st);   // a.rec: record wanted; a.loss_gt: fused loss
-int launch_rollout_fwd_cp_f64(const RolloutArgs<double>& a, int integ, bool forces, bool zmu, hipStream_t st);  // the validation build (rollout_cp_f64.hip)
-bool cp_loss_fusable(const MfRolloutDesc* d);           // the backward of this launch can carry the fused physics loss (either integrator)
-bool cp_loss_in_forward(const MfRolloutDesc* d);        // ... and its forward can accumulate the value itself (LOSS kernels: default integrator)
-long long cp_record_bytes(const MfRolloutDesc* d, int scalar_bytes = 4);      // bytes of the per-step record a launch of this shape writes (0: none)
-
-// one launch of the instantiation the arguments call for (S = float: rollout_fwd_cp_fast.hip; S = double, the validation build:
+// one launch of the instantiation the route calls for (S = float: rollout_fwd_cp_fast.hip; S = double, the validation build:
 // rollout_fwd_cp_f64.hip)
+int launch_rollout_fwd_cp_f32(const RolloutArgs<float>& a, const FwdRoute& r, int integ, hipStream_t st);
+int launch_rollout_fwd_cp_f64(const RolloutArgs<double>& a, const FwdRoute& r, int integ, hipStream_t st);
 template <typename S>
-int launch_rollout_fwd_cp_t(const RolloutArgs<S>& a, int integ, bool forces, bool zmu, hipStream_t st) {
-  // one wave = 4 rollouts: B = 1024 puts one wave on each of the 256 CUs; workgroups of one wave, or of four where the dispatcher would
-  // otherwise stack waves on a SIMD (wave_unit_block; the kernels that carry the fused loss -- <= two waves per CU -- are one-wave workgroups)
-  const long long threads = (long long)a.B * 16;
-  const int block = a.loss_gt ? 64 : (int)wave_unit_block((unsigned)((threads + 63) / 64));
-  const unsigned grid = (unsigned)((threads + block - 1) / block);
-  const bool rec = a.rec != nullptr;
-  if (a.loss_gt) {      // fused physics loss: default integrator, states only (the host checked)
+int launch_rollout_fwd_cp_t(const RolloutArgs<S>& a, const FwdRoute& r, int integ, hipStream_t st) {
+  const int block = r.block;      // one wave = 4 rollouts; workgroups of one wave or of four
+  const unsigned grid = (unsigned)(((long long)a.B * 16 + block - 1) / block);
+  const bool forces = r.forces, zmu = r.zmu;
+  const bool rec = r.record;
+  if (r.loss == kLossInLaunch) {      // fused physics loss: default integrator, states only (the host checked)
     constexpr int I = MF_INTEG_ODEINT_EULER;
     if (rec) { if (zmu) MF_KLAUNCH((rollout_fwd_cp_kernel<S, I, false, true, true, true>), dim3(grid), dim3(block), 0, st, a);
                else MF_KLAUNCH((rollout_fwd_cp_kernel<S, I, false, false, true, true>), dim3(grid), dim3(block), 0, st, a); }

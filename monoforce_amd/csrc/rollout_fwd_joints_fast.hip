@@ -2,7 +2,7 @@
 #include "rollout_fwd_kernel.h"
 
 namespace mf {
-int launch_rollout_fwd_joints_fast_f32(const RolloutArgs<float>& a, LaneMap m, int integ, int block, hipStream_t st) {
-  return launch_rollout_fwd<float, true, true>(a, m, integ, block, st);
+int launch_rollout_fwd_joints_fast_f32(const RolloutArgs<float>& a, const FwdRoute& r, int integ, hipStream_t st) {
+  return launch_rollout_fwd<float, true, true>(a, r, integ, st);
 }
 }  // namespace mf

@@ -23,6 +23,7 @@
 #pragma once
 #include <cstdlib>
 #include "rollout_common.h"
+#include "rollout_route.h"   // LaneMap, FwdRoute
 
 namespace mf {
 
@@ -1032,43 +1033,7 @@ __global__ void __launch_bounds__(G > 256 ? G : 256) rollout_fwd_kernel(const Ro
   if (COST && a.path_cost != nullptr && gl == 0) a.path_cost[b] = M::sqrt(pc_m2 / (pc_n - one));
 }
 
-// Lane mapping for (B, N): G lanes per rollout x PPL points per lane (see the header comment).
-struct LaneMap { int G, PPL; };
-static inline LaneMap choose_lane_map(int B, int N, int points_per_lane) {
-  int g1 = 4;
-  while (g1 < N) g1 <<= 1;  // lanes per rollout at one point per lane
-  // One point per lane whenever the body fits a wave: measured faster than 4 points per lane over the whole range
-  // B = 256 .. 65536 (N = 4) once the fast-math kernels cut the per-lane instruction count (tools/sweep_mapping.py).
-  bool wide = g1 <= 64;
-  if (points_per_lane == 1 && g1 <= 64) wide = true;
-  if (points_per_lane == 4) wide = false;
-  if (N <= 4) return wide ? LaneMap{4, 1} : LaneMap{1, 4};
-  if (N <= 8) return wide ? LaneMap{8, 1} : LaneMap{2, 4};
-  if (N <= 16) return wide ? LaneMap{16, 1} : LaneMap{4, 4};
-  if (N <= 32) return wide ? LaneMap{32, 1} : LaneMap{8, 4};
-  if (N <= 64) return wide ? LaneMap{64, 1} : LaneMap{16, 4};
-  // Larger bodies: one wave per rollout with 2 / 4 / 8 points per lane -- unless the batch is so small that this leaves
-  // most of the chip idle (the reference's own use: 4 .. 64 rollouts of a 175- or 223-point robot).  Then ONE rollout is
-  // spread over 2, 4 or 8 waves of a workgroup, one point per lane (GroupSum exchanges through LDS): ~2.3x fewer instructions
-  // per wave and step.  Measured at N = 223: forward 0.79 vs 1.85 ms, backward 2.0 vs 5.6 ms for B <= 256; 0.98 / 2.9 vs
-  // 1.38 / 4.4 ms at B = 512 (2 waves per SIMD); a tie at B = 1024 -- so up to 2048 waves per launch.
-  if (points_per_lane != 4) {
-    const int g = N <= 128 ? 128 : (N <= 256 ? 256 : 512);
-    if ((long long)B * (g / 64) <= 2 * device_simds()) return LaneMap{g, 1};      // two waves per SIMD (MI355X: 2048)
-  }
-  if (N <= 128) return points_per_lane != 4 ? LaneMap{64, 2} : LaneMap{32, 4};
-  if (N <= 256) return LaneMap{64, 4};
-  return LaneMap{64, 8};
-}
-
-// Instantiated mappings: one point per lane (G = 4..64) and (64, 2/4/8) always; the 4-points-per-lane mappings with G < 64
-// only for the full-output rigid-body kernels (they are a tuning / test option, see choose_lane_map).
-// Round 6: the controls of a saturated launch read ONCE in front of it.  A step loads the next step's (v, w) one step ahead (~0.7 us at
-// 16 384 rollouts) inside its dependent chain, and vmcnt retires loads in order: while the [B][T][2] array sits in the memory-side cache
-// (forward after forward) that is free, but the forward of a fit / train step follows a backward that has streamed ~700 MB through the
-// caches, and every 64-byte line of controls then costs an HBM round trip in front of the step's gathers -- forward 0.34 -> 0.43 ms at
-// 16 384 rollouts, 0.35 again with this 16 us pass (tools/ab_step_fwd2.py, profiles/r6_ab_step_fwd.txt).  A deeper in-kernel prefetch does
-// not help: a load that misses stalls the younger gathers behind it wherever it is issued.  MF_FWD_TOUCH_CONTROLS=0: A/B.
+// the controls of a chunk read ONCE in front of it (where the route asks for it: rollout_route.hip)
 template <int UNUSED = 0>      // (a template: one definition across the translation units that include this header)
 __global__ void __launch_bounds__(256) touch_lines_kernel(const float4* __restrict__ p, long long n16, float4* __restrict__ sink) {
   float4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -1079,35 +1044,27 @@ __global__ void __launch_bounds__(256) touch_lines_kernel(const float4* __restri
   if (acc.x == 1.2345e-30f && acc.y == 5.4321e-30f) *sink = acc;      // (never: keeps the loads)
 }
 template <typename S>
-static inline void touch_controls(const RolloutArgs<S>& a, const LaneMap& m, int b0, int nb, hipStream_t st) {
-  static const bool off = getenv("MF_FWD_TOUCH_CONTROLS") && atoi(getenv("MF_FWD_TOUCH_CONTROLS")) == 0;
-  if (off || a.ctrl_st == 0 || a.ctrl_sb != a.T * 2 || m.G > 64) return;      // (one pair per rollout, or rows that are not adjacent: nothing to stream)
-  if ((long long)nb * m.G < device_simds() / 2 * 64) return;                   // (below half a wave per SIMD a step is longer than the round trip)
+static inline void touch_controls(const RolloutArgs<S>& a, int b0, int nb, hipStream_t st) {
   const long long bytes = (long long)nb * a.T * 2 * (long long)sizeof(S);
-  if (bytes < (8ll << 20) || bytes > (192ll << 20)) return;                    // (a few MB stay resident anyway; more than the cache holds is futile)
   const char* base = reinterpret_cast<const char*>(a.controls + (size_t)b0 * a.ctrl_sb);
   const char* al = reinterpret_cast<const char*>(((uintptr_t)base + 15) & ~(uintptr_t)15);
   const long long n16 = (bytes - (al - base)) / 16;
   hipLaunchKernelGGL((touch_lines_kernel<0>), dim3(2048), dim3(256), 0, st, reinterpret_cast<const float4*>(al), n16, reinterpret_cast<float4*>(const_cast<char*>(al)));
 }
 
+// Instantiated mappings: one point per lane (G = 4..64) and (64, 2/4/8) always; the 4-points-per-lane mappings with G < 64
+// only for the full-output rigid-body kernels (they are a tuning / test option, see choose_lane_map).
 template <typename S, bool FAST, bool JOINTS = false, bool FORCES = true, int COST = 0, bool SPLIT = false, bool ZMU = false>
-int launch_rollout_fwd(const RolloutArgs<S>& a, LaneMap m, int integ, int block, hipStream_t st) {
-  if (m.G > 64) block = m.G;   // a rollout spread over several waves: exactly one rollout per workgroup (LDS + barrier)
-  // More than two waves per SIMD do not help these kernels -- their gathers then miss the CU's L1 more often -- so a very
-  // large batch goes out as consecutive launches of <= kChunkWaves waves on the same stream (measured: B = 65536 1.81 -> 1.73 ms,
-  // B = 131072 4.23 -> 3.90 ms; MF_CHUNK_WAVES=0 disables).  The chunk is a whole number of workgroups; results do not depend on it.
-  static const long long kChunkEnv = getenv("MF_CHUNK_WAVES") ? atoll(getenv("MF_CHUNK_WAVES")) : -1;
-  const long long kChunkWaves = kChunkEnv >= 0 ? kChunkEnv : 2 * device_simds();      // two waves per SIMD (MI355X: 2048)
-  int chunk_B = a.B;
-  if (m.G <= 64 && kChunkWaves > 0 && (long long)a.B * m.G > kChunkWaves * 64) chunk_B = (int)(kChunkWaves * 64 / m.G);
+int launch_rollout_fwd(const RolloutArgs<S>& a, const FwdRoute& r, int integ, hipStream_t st) {
+  const LaneMap m = r.m;
+  const int block = r.block, chunk_B = r.chunk_B;      // a very large batch goes out as consecutive launches on the same stream
   bool launched = false;
   for (int b0 = 0; b0 < a.B; b0 += chunk_B) {
   RolloutArgs<S> ac = a;
   ac.b0 = b0;
-  const long long threads = (long long)((a.B - b0 < chunk_B) ? a.B - b0 : chunk_B) * m.G;
-  const unsigned grid = (unsigned)((threads + block - 1) / block);
-  touch_controls(a, m, b0, (a.B - b0 < chunk_B) ? a.B - b0 : chunk_B, st);
+  const int nb = (a.B - b0 < chunk_B) ? a.B - b0 : chunk_B;
+  const unsigned grid = (unsigned)(((long long)nb * m.G + block - 1) / block);
+  if (nb >= r.touch_lo && nb <= r.touch_hi) touch_controls(a, b0, nb, st);
   launched = false;
 #define MF_CASE(G_, P_)                                                                                                                   \
   if (!launched && m.G == G_ && m.PPL == P_) {                                                                                             \
@@ -1135,19 +1092,19 @@ int launch_rollout_fwd(const RolloutArgs<S>& a, LaneMap m, int integ, int block,
 // The one-point-per-lane mappings (both integrators) with the record for their backward (rollout_bwd_mw_kernel.h):
 // a.rec != NULL.  Bodies of 5..64 points (several rollouts per wave; plain or interleaved maps) and of 65..512 (one per workgroup).
 template <bool FORCES, bool ZMU = false, bool SPLIT = false, typename S = float>
-int launch_rollout_fwd_mw_rec(const RolloutArgs<S>& a, LaneMap m, int integ, hipStream_t st) {
+int launch_rollout_fwd_mw_rec(const RolloutArgs<S>& a, const FwdRoute& r, int integ, hipStream_t st) {
+  const LaneMap m = r.m;
+  const unsigned grid = (unsigned)(((long long)a.B * m.G + r.block - 1) / r.block);
   bool launched = false;
 #define MF_CASE(G_)                                                                                                          \
   if (!launched && m.G == G_ && m.PPL == 1) {                                                                                \
     launched = true;                                                                                                         \
-    const int blk = G_ > 64 ? G_ : 64;                                                                                       \
-    const unsigned grid = (unsigned)(((long long)a.B * G_ + blk - 1) / blk);                                                 \
     if (integ == MF_INTEG_DYNAMICS)                                                                                          \
       MF_KLAUNCH((rollout_fwd_kernel<S, G_, 1, MF_INTEG_DYNAMICS, true, false, FORCES, 0, SPLIT, ZMU, true>),    \
-                         dim3(grid), dim3(blk), 0, st, a);                                                                   \
+                         dim3(grid), dim3(r.block), 0, st, a);                                                               \
     else                                                                                                                     \
       MF_KLAUNCH((rollout_fwd_kernel<S, G_, 1, MF_INTEG_ODEINT_EULER, true, false, FORCES, 0, SPLIT, ZMU, true>), \
-                         dim3(grid), dim3(blk), 0, st, a);                                                                   \
+                         dim3(grid), dim3(r.block), 0, st, a);                                                               \
   }
   MF_CASE(8) MF_CASE(16) MF_CASE(32) MF_CASE(64)
   if constexpr (!ZMU && !SPLIT) { MF_CASE(128) MF_CASE(256) MF_CASE(512) }
@@ -1158,16 +1115,13 @@ int launch_rollout_fwd_mw_rec(const RolloutArgs<S>& a, LaneMap m, int integ, hip
   return MF_OK;
 }
 
-// defined in rollout_fwd_fast.hip
-int launch_rollout_fwd_fast_f32(const RolloutArgs<float>& a, LaneMap m, int integ, int block, bool forces, hipStream_t st);
-// defined in rollout_fwd_split_fast.hip (state stores split over the lanes of a group; one-point-per-lane mappings up to a wave)
-int launch_rollout_fwd_split_fast_f32(const RolloutArgs<float>& a, LaneMap m, int integ, int block, bool forces, hipStream_t st);
-// defined in rollout_fwd_cost.hip
-int launch_rollout_fwd_cost_f32(const RolloutArgs<float>& a, LaneMap m, int integ, int block, bool project, hipStream_t st);
-// defined in rollout_fwd_zmu_fast.hip (shared maps interleaved as (z, mu); one-point-per-lane mappings up to a wave):
-// cost = 0 full outputs (split = state stores spread over the lanes of a group), 1 / 2 cost rows
-int launch_rollout_fwd_zmu_f32(const RolloutArgs<float>& a, LaneMap m, int integ, int block, bool forces, bool split, int cost, hipStream_t st);
-// defined in rollout_fwd_joints_fast.hip
-int launch_rollout_fwd_joints_fast_f32(const RolloutArgs<float>& a, LaneMap m, int integ, int block, hipStream_t st);
+// the float32 fast-math instantiations, one translation unit each
+int launch_rollout_fwd_fast_f32(const RolloutArgs<float>& a, const FwdRoute& r, int integ, hipStream_t st);         // rollout_fwd_fast.hip
+// (state stores split over the lanes of a group; one-point-per-lane mappings up to a wave)
+int launch_rollout_fwd_split_fast_f32(const RolloutArgs<float>& a, const FwdRoute& r, int integ, hipStream_t st);   // rollout_fwd_split_fast.hip
+int launch_rollout_fwd_cost_f32(const RolloutArgs<float>& a, const FwdRoute& r, int integ, hipStream_t st);         // rollout_fwd_cost.hip
+// (shared maps interleaved as (z, mu); one-point-per-lane mappings up to a wave: output rows, plain or split stores, or cost rows)
+int launch_rollout_fwd_zmu_f32(const RolloutArgs<float>& a, const FwdRoute& r, int integ, hipStream_t st);          // rollout_fwd_zmu_fast.hip
+int launch_rollout_fwd_joints_fast_f32(const RolloutArgs<float>& a, const FwdRoute& r, int integ, hipStream_t st);  // rollout_fwd_joints_fast.hip
 
 }  // namespace mf

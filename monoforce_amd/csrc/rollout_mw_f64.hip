@@ -9,13 +9,13 @@
 
 namespace mf {
 
-int launch_rollout_fwd_mw_rec_f64(const RolloutArgs<double>& a, LaneMap m, int integ, bool forces, hipStream_t st) {
-  if (forces) return launch_rollout_fwd_mw_rec<true, false, false, double>(a, m, integ, st);
-  return launch_rollout_fwd_mw_rec<false, false, false, double>(a, m, integ, st);
+int launch_rollout_fwd_mw_rec_f64(const RolloutArgs<double>& a, const FwdRoute& r, int integ, hipStream_t st) {
+  if (r.forces) return launch_rollout_fwd_mw_rec<true, false, false, double>(a, r, integ, st);
+  return launch_rollout_fwd_mw_rec<false, false, false, double>(a, r, integ, st);
 }
 
-int launch_rollout_bwd_mw_f64(const RolloutBwdArgs<double>& a, int G, int integ, bool xs_only, hipStream_t st) {
-  return launch_rollout_bwd_mw_t<double>(a, G, integ, xs_only, st);
+int launch_rollout_bwd_mw_f64(const RolloutBwdArgs<double>& a, const BwdRoute& r, int integ, hipStream_t st) {
+  return launch_rollout_bwd_mw_t<double>(a, r, integ, st);
 }
 
 }  // namespace mf
