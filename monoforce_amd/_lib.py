@@ -13,6 +13,9 @@ LIB_PATH = os.path.join(_HERE, 'csrc', 'libmonoforce_hip.so')
 MF_INTEG_DYNAMICS, MF_INTEG_ODEINT_EULER = 0, 1
 MF_LAYOUT_BATCH_MAJOR, MF_LAYOUT_TIME_MAJOR = 0, 1
 MF_LOSS_VALUE_IN_BACKWARD = 1
+# the answers of mf_rollout_loss_fusable: neither launch carries the loss / both do / the backward alone, of a saturated
+# positions-only launch / the backward alone, of a component-parallel launch in its early-recompute form
+MF_LOSS_FUSE_NONE, MF_LOSS_FUSE_BOTH, MF_LOSS_FUSE_BACKWARD_SATURATED, MF_LOSS_FUSE_BACKWARD_EARLY = 0, 1, 2, 3
 MF_MATH_EXACT, MF_MATH_FAST = 0, 1
 MF_LANES_COMPONENT = 16
 

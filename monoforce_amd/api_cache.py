@@ -123,13 +123,15 @@ class ApiStepCache:
         return (bool(c.use_odeint), float(c.dt), float(c.traj_sim_time), float(c.grid_res), float(c.d_max), float(m.stiffness), float(m.damping),
                 len(m.ts), m.contiguous_outputs, m.precise, m.return_forces, m.points_per_lane, m.snap_to_terrain, m.block, c.integration_mode)
 
-    def forward_key(self, z_grid, controls, friction, joint_angles, state):
+    def forward_key(self, z_grid, controls, friction, joint_angles, state, return_forces):
         """None = this call is not a candidate (then nothing is observed, nothing is replayed)."""
         if (not ENABLED or self.failed or self.bypass or joint_angles is not None or state is not None or not torch.is_grad_enabled()
                 or torch.cuda.is_current_stream_capturing()):
             return None
         m = self.mod
-        if m.contiguous_outputs or m.precise or not m.return_forces:
+        # (`return_forces`: this call's answer, `DPhysics.dphysics(_want_forces=...)`.  The key and the launch-by-launch re-run in
+        #  `_CachedStepFn.backward` read the MODULE's attribute: a call that overrides it is not a candidate)
+        if m.contiguous_outputs or m.precise or not (return_forces and m.return_forces):
             return None
         if not (torch.is_tensor(z_grid) and z_grid.is_cuda and z_grid.dtype == torch.float32 and z_grid.dim() == 3 and torch.is_tensor(controls)
                 and controls.is_cuda and controls.device == z_grid.device and controls.dtype == z_grid.dtype and not controls.requires_grad):

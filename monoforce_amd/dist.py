@@ -95,7 +95,7 @@ class FlatBucket:
 def shared_flat_buffer(tensors):
     """A 1-D view over the storage `tensors` are consecutive slices of, when that storage holds exactly them plus ONE spare
     element behind the last -- or None.  (The shared-map rollout backward hands its map gradients out that way,
-    dphysics_bwd.GradPool.reduce; autograd detaches them on the way into `.grad`, so this goes by storage, not by `_base`.)"""
+    rollout_launch.GradPool.reduce; autograd detaches them on the way into `.grad`, so this goes by storage, not by `_base`.)"""
     tensors = [t for t in tensors if t is not None]
     if not tensors:
         return None

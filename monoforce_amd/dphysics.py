@@ -14,11 +14,14 @@ constructor to get batch-major contiguous tensors instead.
 """
 import ctypes as C
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
-from . import _lib, _timing
+from . import _lib, _timing, rollout_launch as rl
 from .dphys_config import DPhysConfig
+from .dphysics_bwd import rollout_backward
+from .rollout_launch import scalar_suffix as _scalar_suffix, stream_ptr as _stream_ptr
 
 __all__ = ['DPhysics', 'generate_controls', 'vw_to_track_vels', 'inertia_tensor', 'normalized', 'skew_symmetric']
 
@@ -76,23 +79,6 @@ def inertia_tensor(mass, points):
 # ------------------------------------------------------------------------------------------------------------
 # the op
 # ------------------------------------------------------------------------------------------------------------
-def _scalar_suffix(dtype):
-    if dtype == torch.float32:
-        return 'f32'
-    if dtype == torch.float64:
-        return 'f64'
-    raise TypeError(f'DPhysics computes in float32 or float64, got {dtype}')
-
-
-def _stream_ptr(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _is_shared_map(t):
-    """True if a [B,H,W] map is one [H,W] map broadcast over the batch (`expand`, stride 0) -- read once, not B times."""
-    return t.dim() == 3 and (t.shape[0] == 1 or t.stride(0) == 0)
-
-
 def _default_state(controls, B, in_kernel=False):
     """x = 0, xd = (v_0, 0, 0), R = I, omega = (0, 0, w_0) (dphysics.py:554-559).  xd and omega stay differentiable functions
     of the first control when it requires grad (as in the reference); otherwise one launch (mf_rollout_default_state_*), or
@@ -208,157 +194,150 @@ class LossSpec:
         return self._full[B]
 
 
-def _rollout_forward(ctx, mod, z, mu, controls, x_arg, xd0, R0, w0, ts, want_grad, joint_angles=None, want_forces=True,
-                     x0_buf=None, x0_private=False, default_state=False, loss=None):
-    """One `mf_rollout_fwd_*` launch; `loss` = (LossSpec, X_gt[B,T2,3]) fuses physics_loss into it (outs then start with the loss)."""
+class LossRequest(NamedTuple):
+    """physics_loss INSIDE the rollout's launches, as `physics_loss_rollout` asks `dphysics()` for it: the stamps (`spec`), the ground
+    truth X_gt [B,T2,3], whether the backward launch forms the value (MF_LOSS_VALUE_IN_BACKWARD), mf_rollout_loss_fusable's answer
+    (`route`) and whether the force rows are wanted besides."""
+    spec: LossSpec
+    X_gt: torch.Tensor
+    value_in_backward: bool = False
+    route: int = _lib.MF_LOSS_FUSE_BOTH
+    want_forces: bool = False
+
+
+class _Options(NamedTuple):
+    """What `_RolloutFn.apply` / `_RolloutLossFn.apply` take besides the tensors autograd must see.  `x0` is the detached contiguous
+    start position the kernel works on -- it receives the snapped height -- next to the autograd input `x_arg` (the caller's start
+    position when it requires grad); `x0_private`: nobody else sees that buffer."""
+    mod: torch.nn.Module
+    ts: torch.Tensor
+    want_grad: bool
+    want_forces: bool
+    x0: torch.Tensor
+    x0_private: bool
+    default_state: bool
+    loss: Optional[LossRequest] = None
+
+
+def _loss_value_from(loss, mod, integrator, want_grad, want_forces):
+    """Who forms the VALUE of a fused loss: 'backward' -- the backward launch (MF_LOSS_VALUE_IN_BACKWARD; the forward only marks it as
+    not yet known), 'forward' -- the forward rollout kernel accumulates it (`loss_in_forward`; the LOSS kernels: default integrator,
+    component-parallel, states only) -- or 'launch': one small `mf_physics_loss_value_*` launch on the rows just written."""
+    if loss.value_in_backward and want_grad:
+        return 'backward'
+    # (MF_LOSS_FUSE_BACKWARD_SATURATED: the fusion lives in the BACKWARD launch alone)
+    if (mod.loss_in_forward and loss.route != _lib.MF_LOSS_FUSE_BACKWARD_SATURATED and not want_forces
+            and integrator == _lib.MF_INTEG_ODEINT_EULER):
+        return 'forward'
+    return 'launch'
+
+
+def _rollout_forward(ctx, opt, z, mu, controls, x_arg, xd0, R0, w0, joint_angles):
+    """One `mf_rollout_fwd_*` launch; `opt.loss` fuses physics_loss into it (outs then start with the loss)."""
+    mod, want_grad, want_forces, x0, loss = opt.mod, opt.want_grad, opt.want_forces, opt.x0, opt.loss
+    dt, dev = z.dtype, z.device
     # (the library's policy queries -- record bytes, force stride, who stages the interleaved maps -- read the CU count of the CURRENT
     #  device: everything runs with the tensors' device current, not only the launch itself.  ADVICE r4.)
-    with torch.cuda.device(z.device):
-        return _rollout_forward_on_device(ctx, mod, z, mu, controls, x_arg, xd0, R0, w0, ts, want_grad, joint_angles, want_forces,
-                                          x0_buf, x0_private, default_state, loss)
-
-
-def _rollout_forward_on_device(ctx, mod, z, mu, controls, x_arg, xd0, R0, w0, ts, want_grad, joint_angles, want_forces,
-                               x0_buf, x0_private, default_state, loss):
-    # x_arg is the autograd input (the caller's start position when it requires grad); the kernel works on x0_buf, the
-    # detached contiguous buffer that receives the snapped height.  x0_private: nobody else sees that buffer.
-    x0 = x0_buf if x0_buf is not None else x_arg
-    # inference reads a time-constant (expanded) control tensor as it is; the backward kernel wants [B][T][2]
-    controls, sb, st = _kernel_controls(controls, allow_view=not want_grad)
-    desc, keep = mod._make_desc(z, mu, controls)
-    desc.controls_stride_b, desc.controls_stride_t = sb, st
-    desc.default_state = int(default_state)     # the kernel computes the start state and fills x0 / xd0 / R0 / w0
-    if joint_angles is not None:
-        desc.has_joints = 1
-        for i, v in enumerate(sum((list(p) for p in mod.dphys_cfg.joint_positions.values()), [])[:12]):
-            desc.joint_xyz[i] = float(v)
-    B, T, N = desc.B, desc.T, desc.N
-    dt, dev = z.dtype, z.device
-    tm = desc.layout == _lib.MF_LAYOUT_TIME_MAJOR
-    lead = (T, B) if tm else (B, T)
-    new = lambda *tail: torch.empty(*lead, *tail, dtype=dt, device=dev)  # noqa: E731
-    Np = _lib.lib().mf_rollout_force_stride(C.byref(desc))      # point slots per force row the chosen kernel writes
-    if Np < N:
-        raise RuntimeError('mf_rollout_force_stride rejected the descriptor')
-    desc.force_stride = Np
-    Xs, Xds, Rs, Om = new(3), new(3), new(3, 3), new(3)
-    Fs, Ff = (new(Np, 3), new(Np, 3)) if want_forces else (None, None)
-    Xraw = new(3) if want_grad else None
-    # the per-step record of the component-parallel kernels (MfRolloutFwdBufs.rec): kept for the backward where the library
-    # says it pays (few rollouts of a small body), 1 KiB per rollout and step
-    rec = None
-    if want_grad and joint_angles is None:      # (float64: the validation build of the component-parallel kernels, 32-byte quads)
-        rb = _lib.lib().mf_rollout_record_bytes if dt == torch.float32 else _lib.lib().mf_rollout_record_bytes_f64
-        nbytes = int(rb(C.byref(desc)))
-        if nbytes > 0:
-            rec = torch.empty(nbytes // dt.itemsize, dtype=dt, device=dev)
-    zmu_scratch, zmu_staged = _zmu_scratch(mod, desc, keep['z']), mod._staged_zmu(desc, z, mu)
-    bufs = _lib.MfRolloutFwdBufs(
-        z=_lib.ptr(keep['z']), mu=_lib.ptr(keep['mu']), controls=_lib.ptr(controls), ts=_lib.ptr(ts),
-        points=_lib.ptr(keep['points']), part=_lib.ptr(mod._part_dev(dev)),
-        x0=_lib.ptr(x0), xd0=_lib.ptr(xd0), R0=_lib.ptr(R0), w0=_lib.ptr(w0),
-        Xs=_lib.ptr(Xs), Xds=_lib.ptr(Xds), Rs=_lib.ptr(Rs), Omegas=_lib.ptr(Om), Fs=_lib.ptr(Fs), Ff=_lib.ptr(Ff),
-        Xraw=_lib.ptr(Xraw), joint_angles=_lib.ptr(joint_angles),
-        zmu_scratch=_lib.ptr(zmu_scratch), zmu=_lib.ptr(zmu_staged), rec=_lib.ptr(rec))
-    loss_val = lstruct = None
-    in_backward = loss is not None and len(loss) > 2 and bool(loss[2]) and want_grad      # MF_LOSS_VALUE_IN_BACKWARD
-    saturated = loss is not None and len(loss) > 3 and loss[3] == 2      # mf_rollout_loss_fusable = 2: the fusion lives in the BACKWARD launch alone
-    in_forward = (loss is not None and mod.loss_in_forward and not in_backward and not saturated and not want_forces
-                  and desc.integrator == _lib.MF_INTEG_ODEINT_EULER)      # (the LOSS kernels: default integrator, component-parallel)
-    if loss is not None:
-        spec, X_gt = loss[:2]
-        loss_val = torch.empty((), dtype=dt, device=dev)
-    if in_backward and saturated:      # (the saturated forward kernels carry no loss at all: the value is marked as not yet known here)
-        loss_val.fill_(float('nan'))
-    elif in_backward:     # the launch only marks the value as not yet known (NaN); mf_rollout_bwd_* fills it
-        lstruct = _lib.MfRolloutLoss(T2=spec.T2, flags=_lib.MF_LOSS_VALUE_IN_BACKWARD, loss=_lib.ptr(loss_val))
-        bufs.loss = C.cast(C.pointer(lstruct), C.c_void_p)
-    if in_forward:
-        partial = torch.empty((B + 3) // 4, dtype=dt, device=dev)
-        lstruct = _lib.MfRolloutLoss(T2=spec.T2, gt=_lib.ptr(X_gt), near=_lib.ptr(spec.near), w=_lib.ptr(spec.w), row_stamp=_lib.ptr(spec.row_stamp), row_w=_lib.ptr(spec.row_w),
-                                     partial=_lib.ptr(partial), ticket=_lib.ptr(spec.ticket(dev, torch.cuda.current_stream(dev))), loss=_lib.ptr(loss_val))
-        bufs.loss = C.cast(C.pointer(lstruct), C.c_void_p)       # (lstruct stays alive until the launch call below returns)
-    fn = getattr(_lib.lib(), 'mf_rollout_fwd_' + _scalar_suffix(dt))
-    with torch.cuda.device(dev), _timing.timed('rollout_fwd_kernel', dev):
-        _lib.check(fn(C.byref(desc), C.byref(bufs), _stream_ptr(dev)), 'mf_rollout_fwd')
-    _timing.note_launch('rollout_fwd_kernel')
-    outs = (Xs, Xds, Rs, Om) + ((Fs[..., :N, :], Ff[..., :N, :]) if want_forces else ())
-    if tm:
-        outs = tuple(o.transpose(0, 1) for o in outs)
-    if loss is not None and not in_forward and not in_backward:
-        # The VALUE of the loss from one small launch on the rows just written (mf_physics_loss_value_*: gather-reduce over the B x T2
-        # stamped rows, the mean finished inside it).  Measured against the rollout kernel accumulating it itself (LOSS kernels,
-        # `loss_in_forward`): that forward pays ~15 instructions and two loads at EVERY step of a launch bound by the issue slots of
-        # one wave per SIMD -- 0.165 -> 0.185 ms at B = 1024 -- where this launch is 0.012 ms.  The BACKWARD half of the fusion is
-        # the one that pays: no loss-gradient launch, no [T][B][3] gradient rows (rollout_backward).
-        near_b, gt_ts_b = spec.per_rollout(B)
-        Xp = outs[0]
-        ldesc = _lib.MfLossDesc(B=B, T1=T, T2=spec.T2, x_stride_b=Xp.stride(0), x_stride_t=Xp.stride(1), gamma=spec.gamma)
-        lpart = torch.empty((B * spec.T2 + 255) // 256, dtype=dt, device=dev)
-        with torch.cuda.device(dev), _timing.timed('physics_loss_fwd', dev):
-            _lib.check(getattr(_lib.lib(), 'mf_physics_loss_value_' + _scalar_suffix(dt))(
-                C.byref(ldesc), _lib.ptr(Xp), _lib.ptr(X_gt), _lib.ptr(gt_ts_b), _lib.ptr(near_b), _lib.ptr(lpart), _lib.ptr(spec.ticket(dev, torch.cuda.current_stream(dev))),
-                _lib.ptr(loss_val), None, C.c_longlong(0), _stream_ptr(dev)), 'mf_physics_loss_value')
-    if loss is not None:
-        outs = (loss_val,) + outs
-        # (the backward launch's scratch is allocated HERE: under a hipGraph capture the autograd thread must not allocate)
-        # (... and the scalar is held through an ALIAS: the tensor handed out gets this node as its grad_fn, and a node holding its own
-        #  output is a reference cycle -- garbage that the collector then frees whenever it runs, e.g. in the middle of a later capture)
-        # (partial sums of the direction that forms the value: one per workgroup -- B / 4 component-parallel, at most B one point per lane)
-        ctx.loss = (spec, X_gt, Xs, (loss_val.detach(), torch.empty(B if saturated else (B + 3) // 4, dtype=dt, device=dev)) if in_backward else None) if want_grad else None
-    ctx.n_force_outs = 2 if want_forces else 0
-    # outputs the loss does not touch arrive as None in backward (= NULL upstream pointers), not as zero-filled tensors
-    ctx.set_materialize_grads(False)
-    if want_grad:
-        ctx.mod, ctx.desc, ctx.keep = mod, desc, keep
-        # (the backward's record-reading kernel reads the shared maps interleaved too: the staged pair, or this scratch, which it fills itself)
-        ctx.zmu = (zmu_scratch, zmu_staged) if keep['mu'] is not None else (None, None)
-        if ctx.zmu[1] is None and zmu_scratch is not None and dt == torch.float32 and _lib.lib().mf_rollout_fwd_stages_zmu(C.byref(desc)):
-            ctx.zmu = (None, zmu_scratch)       # this launch filled the scratch: the backward reads it as it is
-        ctx.z_shape, ctx.mu_shape, ctx.mu_given = z.shape, (mu.shape if mu is not None else None), mu is not None
-        ctx.z_expanded = z.stride(0) == 0 and z.shape[0] > 1
-        ctx.mu_expanded = mu is not None and mu.stride(0) == 0 and mu.shape[0] > 1
-        ctx.joint_angles = joint_angles.detach() if joint_angles is not None else None
-        ctx.rec = rec
-        # x0 now holds the snapped start position; a caller-visible buffer is copied, the module's own default is not
-        ctx.save_for_backward(controls, x0 if x0_private else x0.clone(), xd0, R0, w0, ts, Xraw, Xds, Rs, Om)
+    with torch.cuda.device(dev):
+        # inference reads a time-constant (expanded) control tensor as it is; the backward kernel wants [B][T][2]
+        controls, sb, st = _kernel_controls(controls, allow_view=not want_grad)
+        desc, maps = mod._make_desc(z, mu, controls)
+        desc.controls_stride_b, desc.controls_stride_t = sb, st
+        desc.default_state = int(opt.default_state)     # the kernel computes the start state and fills x0 / xd0 / R0 / w0
+        if joint_angles is not None:
+            desc.has_joints = 1
+            for i, v in enumerate(sum((list(p) for p in mod.dphys_cfg.joint_positions.values()), [])[:12]):
+                desc.joint_xyz[i] = float(v)
+        B, T, N = desc.B, desc.T, desc.N
+        zmu_scratch, zmu_staged = _zmu_scratch(mod, desc, maps[0]), mod._staged_zmu(desc, z, mu)
+        loss_val = lstruct = value_from = None
+        if loss is not None:
+            spec, X_gt = loss.spec, loss.X_gt
+            saturated = loss.route == _lib.MF_LOSS_FUSE_BACKWARD_SATURATED
+            value_from = _loss_value_from(loss, mod, desc.integrator, want_grad, want_forces)
+            loss_val = torch.empty((), dtype=dt, device=dev)
+            if value_from == 'backward' and saturated:      # (the saturated forward kernels carry no loss at all: the value is marked as not yet known here)
+                loss_val.fill_(float('nan'))
+            elif value_from == 'backward':     # the launch only marks the value as not yet known (NaN); mf_rollout_bwd_* fills it
+                lstruct = rl.loss_struct(spec, flags=_lib.MF_LOSS_VALUE_IN_BACKWARD, loss=loss_val)
+            elif value_from == 'forward':
+                lstruct = rl.loss_struct(spec, X_gt, partial=torch.empty((B + 3) // 4, dtype=dt, device=dev),
+                                         ticket=spec.ticket(dev, torch.cuda.current_stream(dev)), loss=loss_val)
+        # the per-step record of the component-parallel kernels (MfRolloutFwdBufs.rec) is kept for the backward of a rigid body
+        f = rl.launch_forward(desc, maps[0], maps[1], controls, opt.ts, maps[2], mod._part_dev(dev), (x0, xd0, R0, w0),
+                              want_forces=want_forces, want_xraw=want_grad, want_rec=want_grad and joint_angles is None,
+                              joint_angles=joint_angles, zmu_scratch=zmu_scratch, zmu=zmu_staged, loss=lstruct)
+        outs = (f.Xs, f.Xds, f.Rs, f.Om) + ((f.Fs[..., :N, :], f.Ff[..., :N, :]) if want_forces else ())
+        if desc.layout == _lib.MF_LAYOUT_TIME_MAJOR:
+            outs = tuple(o.transpose(0, 1) for o in outs)
+        if value_from == 'launch':
+            # The VALUE of the loss from one small launch on the rows just written (mf_physics_loss_value_*: gather-reduce over the B x T2
+            # stamped rows, the mean finished inside it).  Measured against the rollout kernel accumulating it itself (LOSS kernels,
+            # `loss_in_forward`): that forward pays ~15 instructions and two loads at EVERY step of a launch bound by the issue slots of
+            # one wave per SIMD -- 0.165 -> 0.185 ms at B = 1024 -- where this launch is 0.012 ms.  The BACKWARD half of the fusion is
+            # the one that pays: no loss-gradient launch, no [T][B][3] gradient rows (rollout_backward).
+            near_b, gt_ts_b = spec.per_rollout(B)
+            Xp = outs[0]
+            ldesc = _lib.MfLossDesc(B=B, T1=T, T2=spec.T2, x_stride_b=Xp.stride(0), x_stride_t=Xp.stride(1), gamma=spec.gamma)
+            lpart = torch.empty((B * spec.T2 + 255) // 256, dtype=dt, device=dev)
+            with _timing.timed('physics_loss_fwd', dev):
+                _lib.check(getattr(_lib.lib(), 'mf_physics_loss_value_' + _scalar_suffix(dt))(
+                    C.byref(ldesc), _lib.ptr(Xp), _lib.ptr(X_gt), _lib.ptr(gt_ts_b), _lib.ptr(near_b), _lib.ptr(lpart), _lib.ptr(spec.ticket(dev, torch.cuda.current_stream(dev))),
+                    _lib.ptr(loss_val), None, C.c_longlong(0), _stream_ptr(dev)), 'mf_physics_loss_value')
+        if loss is not None:
+            outs = (loss_val,) + outs
+            # (the backward launch's scratch is allocated HERE: under a hipGraph capture the autograd thread must not allocate)
+            # (... and the scalar is held through an ALIAS: the tensor handed out gets this node as its grad_fn, and a node holding its own
+            #  output is a reference cycle -- garbage that the collector then frees whenever it runs, e.g. in the middle of a later capture)
+            # (partial sums of the direction that forms the value: one per workgroup -- B / 4 component-parallel, at most B one point per lane)
+            in_backward = value_from == 'backward'
+            ctx.loss = (spec, X_gt, f.Xs, (loss_val.detach(), torch.empty(B if saturated else (B + 3) // 4, dtype=dt, device=dev)) if in_backward else None) if want_grad else None
+        # outputs the loss does not touch arrive as None in backward (= NULL upstream pointers), not as zero-filled tensors
+        ctx.set_materialize_grads(False)
+        if want_grad:
+            ctx.mod, ctx.desc, ctx.maps = mod, desc, maps
+            # (the backward's record-reading kernel reads the shared maps interleaved too: the staged pair, or this scratch, which it fills itself)
+            ctx.zmu = (zmu_scratch, zmu_staged) if maps[1] is not None else (None, None)
+            if ctx.zmu[1] is None and zmu_scratch is not None and dt == torch.float32 and _lib.lib().mf_rollout_fwd_stages_zmu(C.byref(desc)):
+                ctx.zmu = (None, zmu_scratch)       # this launch filled the scratch: the backward reads it as it is
+            ctx.z_shape, ctx.mu_shape = z.shape, (mu.shape if mu is not None else None)
+            ctx.z_expanded = z.stride(0) == 0 and z.shape[0] > 1
+            ctx.mu_expanded = mu is not None and mu.stride(0) == 0 and mu.shape[0] > 1
+            ctx.joint_angles = joint_angles.detach() if joint_angles is not None else None
+            ctx.rec = f.rec
+            # x0 now holds the snapped start position; a caller-visible buffer is copied, the module's own default is not
+            ctx.save_for_backward(controls, x0 if opt.x0_private else x0.clone(), xd0, R0, w0, opt.ts, f.Xraw, f.Xds, f.Rs, f.Om)
     return outs
 
 
 class _RolloutFn(torch.autograd.Function):
-    """forward = mf_rollout_fwd_*; backward = mf_rollout_bwd_* (reverse-time adjoint of the same scan)."""
+    """forward = mf_rollout_fwd_*; backward = mf_rollout_bwd_* (reverse-time adjoint of the same scan).  `opt` (`_Options`) carries
+    everything that is not a differentiable tensor."""
 
     @staticmethod
-    def forward(ctx, mod, z, mu, controls, x_arg, xd0, R0, w0, ts, want_grad, joint_angles=None, want_forces=True,
-                x0_buf=None, x0_private=False, default_state=False):
-        return _rollout_forward(ctx, mod, z, mu, controls, x_arg, xd0, R0, w0, ts, want_grad, joint_angles, want_forces,
-                                x0_buf, x0_private, default_state)
+    def forward(ctx, opt, z, mu, controls, x_arg, xd0, R0, w0, joint_angles):
+        return _rollout_forward(ctx, opt, z, mu, controls, x_arg, xd0, R0, w0, joint_angles)
 
     @staticmethod
     def backward(ctx, gXs, gXds, gRs, gOm, gFs=None, gFf=None):
-        from .dphysics_bwd import rollout_backward
-        return rollout_backward(ctx, gXs, gXds, gRs, gOm, gFs, gFf) + (None, None, None, None)
+        return (None,) + rollout_backward(ctx, (gXs, gXds, gRs, gOm, gFs, gFf))
 
 
 class _RolloutLossFn(torch.autograd.Function):
-    """The rollout with `physics_loss` inside both launches (MfRolloutLoss): outputs (loss, Xs, Xds, Rs, Omegas), of which only the
-    loss is differentiable -- the backward forms dL/dXs itself at the stamped rows."""
+    """The rollout with `physics_loss` inside both launches (MfRolloutLoss; `opt.loss`): outputs (loss, Xs, Xds, Rs, Omegas[, forces]), of
+    which only the loss is differentiable -- the backward forms dL/dXs itself at the stamped rows."""
 
     @staticmethod
-    def forward(ctx, mod, z, mu, controls, x_arg, xd0, R0, w0, ts, want_grad, x0_buf, x0_private, default_state, spec, X_gt,
-                value_in_backward=False, route=1, want_forces=False):
-        outs = _rollout_forward(ctx, mod, z, mu, controls, x_arg, xd0, R0, w0, ts, want_grad, None, bool(want_forces), x0_buf, x0_private,
-                                default_state, loss=(spec, X_gt, value_in_backward, route))
+    def forward(ctx, opt, z, mu, controls, x_arg, xd0, R0, w0, joint_angles):
+        outs = _rollout_forward(ctx, opt, z, mu, controls, x_arg, xd0, R0, w0, joint_angles)
         ctx.mark_non_differentiable(*outs[1:])
         return outs
 
     @staticmethod
     def backward(ctx, gloss, *_unused):
-        from .dphysics_bwd import rollout_backward
         if gloss is None:
-            return (None,) * 18
-        grads = rollout_backward(ctx, None, None, None, None, None, None, gloss=gloss)      # (mod, z, mu, controls, x, xd0, R0, w0, ts, want_grad, ja)
-        return grads[:10] + (None, None, None, None, None, None, None, None)
+            return (None,) * len(ctx.needs_input_grad)
+        return (None,) + rollout_backward(ctx, (None,) * 6, gloss=gloss)
 
 
 class DPhysics(torch.nn.Module):
@@ -436,53 +415,45 @@ class DPhysics(torch.nn.Module):
         self.staged_handoffs += 1
         return zmu
 
+    def _integrator(self):
+        return _lib.MF_INTEG_ODEINT_EULER if self.dphys_cfg.use_odeint else _lib.MF_INTEG_DYNAMICS
+
+    def _query_desc(self, B, T, z_grid, **options):
+        """A descriptor that only asks the library a policy query: this module's shapes, integrator and lane mapping, no constants."""
+        return rl.rollout_desc(B, T, self.x_points.shape[1], z_grid.shape[-2], z_grid.shape[-1], self._integrator(),
+                               points_per_lane=self.points_per_lane, **options)
+
     def _make_desc(self, z, mu, controls):
+        """(descriptor of one launch, (z, mu, points) as the kernels read them)."""
         cfg = self.dphys_cfg
-        B = controls.shape[0]
-        assert z.dim() == 3, f'z_grid must be [B,H,W] (or [1,H,W] = one map shared by all rollouts), got {tuple(z.shape)}'
-        _, H, W = z.shape
-        for name, m in (('z_grid', z), ('friction', mu)):
-            if m is None:
-                continue
-            assert m.dim() == 3 and tuple(m.shape[-2:]) == (H, W), \
-                f'{name} shape {tuple(m.shape)} does not match the {H}x{W} height grid'
-            assert m.shape[0] in (1, B), f'{name} batch {m.shape[0]} is neither 1 (shared map) nor the {B} rollouts of controls'
-        shared = _is_shared_map(z) and (mu is None or _is_shared_map(mu))
-        if shared:
-            zc = z[0].contiguous()
-            muc = None if mu is None else mu[0].contiguous()
-        else:
-            # one map shared, the other per rollout: the kernels index both at b*H*W, so the shared one is expanded for real
-            zc = z.expand(B, H, W).contiguous()
-            muc = None if mu is None else mu.expand(B, H, W).contiguous()
-        integ = _lib.MF_INTEG_ODEINT_EULER if cfg.use_odeint else _lib.MF_INTEG_DYNAMICS
+        B, T = controls.shape[:2]
+        zc, muc, shared = rl.canonical_maps(z, mu, B)
         if cfg.integration_mode != 'euler':
             # the reference's 'rk4' is a degenerate formula on the custom loop and an adaptive-free torchdiffeq solver on
             # the other; neither is part of the parity scope (SURVEY.md 8a2)
             raise ValueError(f'Unknown integration mode: {cfg.integration_mode}' if cfg.integration_mode != 'rk4' else
                              "integration_mode 'rk4' is not supported by the HIP rollout (only 'euler')")
-        desc = _lib.MfRolloutDesc(
-            B=controls.shape[0], T=controls.shape[1], N=self.x_points.shape[1], H=H, W=W,
-            n_tracks=len(cfg.driving_parts), integrator=integ,
-            layout=_lib.MF_LAYOUT_BATCH_MAJOR if self.contiguous_outputs else _lib.MF_LAYOUT_TIME_MAJOR,
+        consts = dict(mass=float(cfg.robot_mass), gravity=float(cfg.gravity), stiffness=float(self.stiffness), damping=float(self.damping),
+                      omega_max=float(cfg.omega_max), grid_res=float(cfg.grid_res), d_max=float(cfg.d_max), dt=float(cfg.dt),
+                      robot_size_y=float(cfg.robot_size[1]))
+        desc = rl.rollout_desc(
+            B, T, self.x_points.shape[1], z.shape[1], z.shape[2], self._integrator(), consts=consts, Iinv=self._iinv(z.dtype),
+            n_tracks=len(cfg.driving_parts), layout=_lib.MF_LAYOUT_BATCH_MAJOR if self.contiguous_outputs else _lib.MF_LAYOUT_TIME_MAJOR,
             map_shared=int(shared), block=self.block, skip_snap=int(not self.snap_to_terrain), points_per_lane=self.points_per_lane,
-            math_mode=_lib.MF_MATH_EXACT if self.precise else _lib.MF_MATH_FAST,
-            mass=float(cfg.robot_mass), gravity=float(cfg.gravity), stiffness=float(self.stiffness),
-            damping=float(self.damping), omega_max=float(cfg.omega_max), grid_res=float(cfg.grid_res),
-            d_max=float(cfg.d_max), dt=float(cfg.dt), robot_size_y=float(cfg.robot_size[1]))
-        for i, v in enumerate(self._iinv(z.dtype)):
-            desc.Iinv[i] = v
-        keep = dict(z=zc, mu=muc, points=self._points_dev(z.device, z.dtype))
-        return desc, keep
+            math_mode=_lib.MF_MATH_EXACT if self.precise else _lib.MF_MATH_FAST)
+        return desc, (zc, muc, self._points_dev(z.device, z.dtype))
 
     # -- reference API --------------------------------------------------------------------------------------
-    def dphysics(self, z_grid, controls, joint_angles=None, state=None, friction=None, _loss=None):
+    def dphysics(self, z_grid, controls, joint_angles=None, state=None, friction=None, _loss=None, _want_forces=None):
         """Simulate the robot on the terrain (dphysics.py:530-594).
 
         z_grid (B,H,W), controls (B,N,2), joint_angles (B,N,4) or None, state=(x,xd,R,omega) or None, friction (B,H,W).
         Returns ((Xs,Xds,Rs,Omegas), (F_springs,F_frictions)).
+        `_loss` (a `LossRequest`): physics_loss inside the launches (physics_loss_rollout).  `_want_forces`: this call's answer to
+        `return_forces` (default: the module's) -- a caller that only consumes the states asks for the states-only kernels.
         """
         cfg = self.dphys_cfg
+        return_forces = self.return_forces if _want_forces is None else bool(_want_forces)
         dev = torch.device(self.device)
         dt_, T_ = cfg.dt, cfg.traj_sim_time
         # the drop-in step at the fused step's speed (api_cache.py): after a few identical forward -> physics_loss cycles the whole step is
@@ -493,7 +464,7 @@ class DPhysics(torch.nn.Module):
             if cache is None:
                 from .api_cache import ApiStepCache
                 cache = self.__dict__['_api_step_cache'] = ApiStepCache(self)
-            api_key = cache.forward_key(z_grid, controls, friction, joint_angles, state)
+            api_key = cache.forward_key(z_grid, controls, friction, joint_angles, state, return_forces)
             if api_key is not None:
                 hit = cache.try_forward(api_key, z_grid, controls, friction)
                 if hit is not None:
@@ -550,32 +521,27 @@ class DPhysics(torch.nn.Module):
         # buffers (mf_rollout_fwd_f64), so they stay (N > 4 under no_grad, or B beyond the record range)
         cp64 = dtype == torch.float64 and self.points_per_lane == _lib.MF_LANES_COMPONENT and ja_dev is None
         if cp64 and self.x_points.shape[1] > 4:
-            dq = _lib.MfRolloutDesc(B=B, T=N_ts, N=self.x_points.shape[1], H=z_grid.shape[-2], W=z_grid.shape[-1], n_tracks=len(cfg.driving_parts),
-                                    integrator=_lib.MF_INTEG_ODEINT_EULER if cfg.use_odeint else _lib.MF_INTEG_DYNAMICS,
-                                    points_per_lane=self.points_per_lane, math_mode=_lib.MF_MATH_FAST)
+            dq = self._query_desc(B, N_ts, z_grid, n_tracks=len(cfg.driving_parts))
             with torch.cuda.device(dev):
-                cp64 = want_grad and int(_lib.lib().mf_rollout_record_bytes_f64(C.byref(dq))) > 0
-        want_forces = self.return_forces or self.precise or (dtype != torch.float32 and not cp64) or ja_dev is not None
+                cp64 = want_grad and int(rl.record_bytes(dq, dtype)) > 0
+        want_forces = return_forces or self.precise or (dtype != torch.float32 and not cp64) or ja_dev is not None
         # a start position that requires grad is the autograd input itself (its gradient: x and y through the contact geometry,
         # z none -- the snap overwrites it); the kernel works on the detached buffer x0 either way
         x_arg = x_in if (want_grad and x_in.requires_grad) else x0
+        if _loss is not None:       # physics_loss inside the launches (physics_loss_rollout): the request says whether the forces are written
+            want_forces = bool(_loss.want_forces)
+        opt = _Options(self, ts, want_grad, want_forces, x0, own_state, state_in_kernel, _loss)
+        outs = (_RolloutFn if _loss is None else _RolloutLossFn).apply(opt, z_grid, friction, controls, x_arg, xd0, R0, w0, ja_dev)
         loss_val = None
-        if _loss is not None:       # physics_loss inside the launches (physics_loss_rollout)
-            spec, X_gt = _loss[:2]
-            outs = _RolloutLossFn.apply(self, z_grid, friction, controls, x_arg, xd0, R0, w0, ts, want_grad, x0, own_state,
-                                        state_in_kernel, spec, X_gt, len(_loss) > 2 and bool(_loss[2]), _loss[3] if len(_loss) > 3 else 1,
-                                        len(_loss) > 4 and bool(_loss[4]))
+        if _loss is not None:
             loss_val, outs = outs[0], outs[1:]
-        else:
-            outs = _RolloutFn.apply(self, z_grid, friction, controls, x_arg, xd0, R0, w0, ts, want_grad, ja_dev, want_forces,
-                                    x0, own_state, state_in_kernel)
         if not aliased:
             with torch.no_grad():       # the reference's in-place write (through .data: no version bump on a tensor autograd saved)
                 x_in.data[..., 2] = x0[..., 2].to(device=x_in.device, dtype=x_in.dtype)
         Xs, Xds, Rs, Omegas = outs[:4]
         F_springs, F_frictions = outs[4:] if len(outs) == 6 else (None, None)
         if _loss is not None:
-            if len(_loss) > 4 and _loss[4]:
+            if _loss.want_forces:
                 return loss_val, (Xs, Xds, Rs, Omegas), (F_springs, F_frictions)
             return loss_val, (Xs, Xds, Rs, Omegas)
         if api_key is not None:
@@ -601,7 +567,7 @@ class DPhysics(torch.nn.Module):
         `value_in_backward` (MF_LOSS_VALUE_IN_BACKWARD): for a caller that ALWAYS calls `loss.backward()` next and reads the value
         only afterwards (a fit loop): the backward launch forms the value too -- the returned scalar is NaN until then -- and the
         step loses its one remaining loss launch.
-        Where the library cannot fuse (mf_rollout_loss_fusable: 1 = float32 fast math, a rigid body of <= 4 points, <= 2048 rollouts --
+        Where the library cannot fuse (mf_rollout_loss_fusable, the MF_LOSS_FUSE_* answers of _lib.py: 1 = float32 fast math, a rigid body of <= 4 points, <= 2048 rollouts --
         dynamics(): <= 1024; 2 = the saturated positions-only backward, > 8192 rollouts of a <= 4-point body, whose forward takes the value
         from one small launch on its rows; 3 = the early-recompute component-parallel backward, 4097 .. 8192 rollouts, likewise; 0 in between
         -- 2049 .. 4096 rollouts, dynamics() 1025 .. 4096: the loss's own two launches are cheaper there; several stamps on one row: never)
@@ -614,32 +580,26 @@ class DPhysics(torch.nn.Module):
         if ok:
             ok = spec.T == min(int(self.dphys_cfg.traj_sim_time / self.dphys_cfg.dt), controls.shape[1])
         if ok:
-            d = _lib.MfRolloutDesc(B=B, T=spec.T, N=self.x_points.shape[1], H=z_grid.shape[-2], W=z_grid.shape[-1],
-                                   integrator=_lib.MF_INTEG_ODEINT_EULER if self.dphys_cfg.use_odeint else _lib.MF_INTEG_DYNAMICS,
-                                   math_mode=_lib.MF_MATH_FAST, force_stride=max(self.x_points.shape[1], 4), map_shared=1, layout=_lib.MF_LAYOUT_TIME_MAJOR,
-                                   points_per_lane=self.points_per_lane)
+            d = self._query_desc(B, spec.T, z_grid, force_stride=max(self.x_points.shape[1], 4), map_shared=1, layout=_lib.MF_LAYOUT_TIME_MAJOR)
             with torch.cuda.device(torch.device(self.device)):
                 fus = int(_lib.lib().mf_rollout_loss_fusable(C.byref(d)))
-            # (2: the saturated positions-only backward forms dL/dXs itself -- and the value, with `value_in_backward`; else the value comes
+            # (saturated: the positions-only backward forms dL/dXs itself -- and the value, with `value_in_backward`; else the value comes
             #  from one small launch on the forward's rows)
-            ok = fus == 1 or (fus in (2, 3) and z_grid.dtype == torch.float32)
-            if fus == 3:       # (the one-wave component-parallel backward forms dL/dXs; the value: one small launch on the forward's rows)
+            ok = fus == _lib.MF_LOSS_FUSE_BOTH or (fus in (_lib.MF_LOSS_FUSE_BACKWARD_SATURATED, _lib.MF_LOSS_FUSE_BACKWARD_EARLY)
+                                                   and z_grid.dtype == torch.float32)
+            if fus == _lib.MF_LOSS_FUSE_BACKWARD_EARLY:       # (the one-wave component-parallel backward forms dL/dXs; the value: one small launch on the forward's rows)
                 value_in_backward = False
         if not ok:
             # (the loss reads the positions only: the forward writes the states, not the 24 N bytes of force rows per rollout-step -- for the
-            #  reference's 223-point body 36 of 241 MB per launch; `return_forces` is restored for the module's other callers)
-            keep, self.return_forces = self.return_forces, bool(want_forces)
-            try:
-                states, forces = self.dphysics(z_grid, controls, state=state, friction=friction)
-            finally:
-                self.return_forces = keep
+            #  reference's 223-point body 36 of 241 MB per launch)
+            states, forces = self.dphysics(z_grid, controls, state=state, friction=friction, _want_forces=want_forces)
             B_, T2 = X_gt.shape[:2]
             gt_ts = spec.gt_ts.unsqueeze(0).expand(B_, -1)
             loss = physics_loss_fused(states, [X_gt], None, gt_ts, gamma=spec.gamma, nearest=spec.near.unsqueeze(0).expand(B_, -1))
             return (loss, states, forces) if want_forces else (loss, states)
         Xg = X_gt.detach().to(device=torch.device(self.device), dtype=z_grid.dtype).contiguous()
         assert Xg.shape == (B, spec.T2, 3), f'X_gt shape {tuple(Xg.shape)} != {(B, spec.T2, 3)}'
-        return self.dphysics(z_grid, controls, state=state, friction=friction, _loss=(spec, Xg, bool(value_in_backward), fus, bool(want_forces)))
+        return self.dphysics(z_grid, controls, state=state, friction=friction, _loss=LossRequest(spec, Xg, bool(value_in_backward), fus, bool(want_forces)))
 
     @torch.no_grad()
     def rollout_costs(self, z_grid, controls, state=None, friction=None, pose_stride=None, project=True):
@@ -679,27 +639,19 @@ class DPhysics(torch.nn.Module):
             friction = friction.to(device=dev, dtype=torch.float32)
         ps = int(pose_stride) if pose_stride else max(int(0.5 / cfg.dt), 1)
         ts = self._time_grid(N_ts, torch.float32, dev)
-        desc, keep = self._make_desc(z_grid, friction, controls)
-        desc.controls_stride_b, desc.controls_stride_t = sb, st
-        desc.layout, desc.pose_stride, desc.cost_project = _lib.MF_LAYOUT_TIME_MAJOR, ps, int(bool(project))
-        desc.default_state = int(state_in_kernel)
         Tp = 1 + (N_ts - 1 + ps - 1) // ps
-        rows = torch.empty(N_ts, B, 4, device=dev)
-        force_cost = torch.empty(B, device=dev)
-        Xs, Rs = torch.empty(Tp, B, 3, device=dev), torch.empty(Tp, B, 3, 3, device=dev)
-        bufs = _lib.MfRolloutFwdBufs(
-            z=_lib.ptr(keep['z']), mu=_lib.ptr(keep['mu']), controls=_lib.ptr(controls), ts=_lib.ptr(ts),
-            points=_lib.ptr(keep['points']), part=_lib.ptr(self._part_dev(dev)),
-            x0=_lib.ptr(x0), xd0=_lib.ptr(xd0), R0=_lib.ptr(R0), w0=_lib.ptr(w0),
-            Xs=_lib.ptr(Xs), Xds=None, Rs=_lib.ptr(Rs), Omegas=None, Fs=None, Ff=None, Xraw=None, joint_angles=None,
-            cost_rows=_lib.ptr(rows), path_cost=_lib.ptr(force_cost), zmu_scratch=_lib.ptr(_zmu_scratch(self, desc, keep['z'])))
-        with torch.cuda.device(dev), _timing.timed('rollout_fwd_kernel', dev):
-            _lib.check(_lib.lib().mf_rollout_fwd_f32(C.byref(desc), C.byref(bufs), _stream_ptr(dev)), 'mf_rollout_fwd')
+        with torch.cuda.device(dev):
+            desc, (zc, muc, points) = self._make_desc(z_grid, friction, controls)
+            desc.controls_stride_b, desc.controls_stride_t = sb, st
+            desc.layout, desc.pose_stride, desc.cost_project = _lib.MF_LAYOUT_TIME_MAJOR, ps, int(bool(project))
+            desc.default_state = int(state_in_kernel)
+            f = rl.launch_forward(desc, zc, muc, controls, ts, points, self._part_dev(dev), (x0, xd0, R0, w0), pose_rows=Tp,
+                                  zmu_scratch=_zmu_scratch(self, desc, zc))
         key = ('pose_steps', Tp, ps, N_ts, str(dev))
         if key not in self._cache:       # constant per configuration: no two extra launches per planning cycle
             self._cache[key] = torch.clamp(torch.arange(Tp, device=dev) * ps, max=N_ts - 1)
         steps = self._cache[key]
-        return dict(cost_rows=rows.transpose(0, 1), Xs=Xs.transpose(0, 1), Rs=Rs.transpose(0, 1), pose_steps=steps, force_cost=force_cost)
+        return dict(cost_rows=f.cost_rows.transpose(0, 1), Xs=f.Xs.transpose(0, 1), Rs=f.Rs.transpose(0, 1), pose_steps=steps, force_cost=f.path_cost)
 
     def interpolate_grid(self, grid, x_query, y_query, return_normals=False, return_cells=False):
         """The reference's public sampling method (dphysics.py:385-455), bug for bug, as one HIP launch
@@ -735,14 +687,11 @@ class DPhysics(torch.nn.Module):
         return out[0] if len(out) == 1 else out
 
     def _time_grid(self, n, dtype, dev):
-        key = ('ts', n, dtype, str(dev))
-        if key not in self._cache:
-            self._cache[key] = torch.linspace(0, self._ts_T, self._ts_full_len, dtype=dtype)[:n].to(dev).contiguous()
-        return self._cache[key]
+        return rl.time_grid(self._ts_T, self._ts_full_len, n, dtype, dev)
 
-    def forward(self, z_grid, controls, joint_angles=None, state=None, vis=False, friction=None):
+    def forward(self, z_grid, controls, joint_angles=None, state=None, vis=False, friction=None, _want_forces=None):
         states, forces = self.dphysics(z_grid=z_grid, controls=controls, joint_angles=joint_angles, state=state,
-                                       friction=friction)
+                                       friction=friction, _want_forces=_want_forces)
         if vis:
             with torch.no_grad():
                 self.visualize(states=states, z_grid=z_grid)

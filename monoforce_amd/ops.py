@@ -34,15 +34,15 @@ The three MPPI ops (float32, no autograd; monoforce_amd/mppi.py is their consume
 [2] on the device, `weights` = (inclination, force, goal) with `force_cost` given exactly when the force weight is non-zero; `best` / `n_valid`
 are int32 [1] on the device.
 
-`DPhysics` itself keeps calling the C ABI through its own autograd function (monoforce_amd/dphysics.py) -- same library calls,
-more options (articulated bodies, path costs, strided controls); `rollout()` / `splat()` below are the functional entries.
+The rollout ops and `DPhysics`'s own autograd function (monoforce_amd/dphysics.py: more options -- articulated bodies, path costs,
+strided controls) launch through the same marshalling (monoforce_amd/rollout_launch.py); `rollout()` / `splat()` below are the
+functional entries.
 """
 import ctypes as C
 
 import torch
 
-from . import _lib, _timing
-from .dphysics_bwd import grad_copies_for, grad_pool
+from . import _lib, _timing, rollout_launch as rl
 
 
 class _PoolOwner:       # the registered ops have no module to hang the persistent gradient-copy pools on
@@ -81,131 +81,63 @@ def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-def _rollout_desc(z, controls, pts, Iinv, consts, integrator):
-    assert len(consts) in (len(CONST_NAMES), len(CONST_NAMES) + 1), f'consts = {CONST_NAMES} (+ traj_sim_time)'
-    c = dict(zip(CONST_NAMES, (float(v) for v in consts)))
-    B, T = controls.shape[:2]
-    assert z.dim() == 3 and z.shape[0] in (1, B), 'z must be [B,H,W] or [1,H,W] (one map shared by all rollouts)'
-    d = _lib.MfRolloutDesc(B=B, T=T, N=pts.shape[0], H=z.shape[1], W=z.shape[2], n_tracks=2, integrator=int(integrator),
-                           layout=_lib.MF_LAYOUT_TIME_MAJOR, map_shared=int(z.shape[0] == 1), math_mode=_lib.MF_MATH_FAST,
-                           mass=c['mass'], gravity=c['gravity'], stiffness=c['stiffness'], damping=c['damping'], omega_max=c['omega_max'],
-                           grid_res=c['grid_res'], d_max=c['d_max'], dt=c['dt'], robot_size_y=c['robot_size_y'])
-    for i, v in enumerate(Iinv.detach().double().flatten().tolist()):      # 9 host scalars (a device read: build the op's inputs once)
-        d.Iinv[i] = v
-    return d
-
-
-_TS = {}
-
-
 def _time_grid(consts, T, dt, dev):
     """The reference's grid: linspace(0, T_sim, int(T_sim / dt))[:T] (dphysics.py:166-167, 581); T_sim defaults to T * dt."""
     step = float(consts[6])
     t_sim = float(consts[9]) if len(consts) > 9 else T * step
-    key = (step, t_sim, T, dt, str(dev))
-    if key not in _TS:       # built once per configuration: a host-to-device copy is not allowed while a stream is capturing
-        _TS[key] = torch.linspace(0, t_sim, max(int(t_sim / step), T), dtype=dt)[:T].to(dev).contiguous()
-    return _TS[key]
+    return rl.time_grid(t_sim, max(int(t_sim / step), T), T, dt, dev)
 
 
-def _prep(z, mu, controls, pts, part_id, states=()):
-    """Inputs in the kernels' dtype and layout, after the shape checks `DPhysics._make_desc` applies to the module path: both maps
-    [1 or B, H, W] over the same H x W; when one is shared and the other per rollout the kernels index both at b*H*W, so the shared
-    one is expanded for real (the backward sums its gradient back over the rollouts); every start-state tensor has the B rows of
-    `controls`."""
+def _prep(z, mu, controls, pts, part_id, Iinv, consts, integrator, states):
+    """(descriptor, z, mu, controls, pts, part_id, state, ts) in the kernels' dtype and layout.  The maps go through the same checks and
+    canonical form as on the module path (`rollout_launch.canonical_maps`), except that here only a [1,H,W] map counts as shared -- an
+    expanded one (stride 0) is read per rollout; every start-state tensor has the B rows of `controls`."""
     dt = z.dtype
-    B = controls.shape[0]
+    assert len(consts) in (len(CONST_NAMES), len(CONST_NAMES) + 1), f'consts = {CONST_NAMES} (+ traj_sim_time)'
     assert controls.dim() == 3 and controls.shape[2] == 2, f'controls must be [B,T,2], got {tuple(controls.shape)}'
-    assert z.dim() == 3 and z.shape[0] in (1, B), f'z must be [B,H,W] or [1,H,W] (one map shared by all {B} rollouts), got {tuple(z.shape)}'
-    if mu is not None:
-        assert mu.dim() == 3 and tuple(mu.shape[1:]) == tuple(z.shape[1:]), \
-            f'mu shape {tuple(mu.shape)} does not match the {z.shape[1]}x{z.shape[2]} height grid'
-        assert mu.shape[0] in (1, B), f'mu batch {mu.shape[0]} is neither 1 (shared map) nor the {B} rollouts of controls'
-        if mu.shape[0] != z.shape[0]:
-            z, mu = z.expand(B, -1, -1), mu.expand(B, -1, -1)
-    for name, t in states:
+    B, T = controls.shape[:2]
+    for name, t in zip(('x0', 'xd0', 'R0', 'w0'), states):
         assert t.shape[0] == B, f'{name} has {t.shape[0]} rows, controls {B} rollouts'
     assert pts.dim() == 2 and pts.shape[1] == 3 and part_id.shape[0] == pts.shape[0], 'pts must be [N,3] with one part id per point'
-    cont = lambda t: None if t is None else t.to(dt).contiguous()  # noqa: E731
-    return cont(z), cont(mu), cont(controls), cont(pts), part_id.to(torch.int32).contiguous()
+    unshare = lambda m: m if m is None or m.shape[0] == 1 else m.to(dt).contiguous()  # noqa: E731
+    zc, muc, shared = rl.canonical_maps(unshare(z), unshare(None if mu is None else mu.to(dt)), B)
+    # (n_tracks = 2: the ops' schema carries no track count.  Iinv: 9 host scalars -- a device read: build the op's inputs once)
+    d = rl.rollout_desc(B, T, pts.shape[0], z.shape[1], z.shape[2], int(integrator), consts=dict(zip(CONST_NAMES, (float(v) for v in consts))),
+                        Iinv=Iinv.detach().double().flatten().tolist(), n_tracks=2, layout=_lib.MF_LAYOUT_TIME_MAJOR, map_shared=int(shared),
+                        math_mode=_lib.MF_MATH_EXACT if dt == torch.float64 else _lib.MF_MATH_FAST)
+    return (d, zc, muc, controls.to(dt).contiguous(), pts.to(dt).contiguous(), part_id.to(torch.int32).contiguous(),
+            tuple(t.to(dt).contiguous() for t in states), _time_grid(consts, T, dt, z.device))
 
 
 @torch.library.impl(_L, 'dphys_rollout_fwd', 'CUDA')
 def _rollout_fwd(z, mu, controls, x0, xd0, R0, w0, pts, part_id, Iinv, consts, integrator, save_for_bwd):
-    dev, dt = z.device, z.dtype
-    zc, muc, cc, pc, part = _prep(z, mu, controls, pts, part_id, (('x0', x0), ('xd0', xd0), ('R0', R0), ('w0', w0)))
-    d = _rollout_desc(zc, cc, pc, Iinv, consts, integrator)
-    if dt == torch.float64:
-        d.math_mode = _lib.MF_MATH_EXACT
-    B, T, N = d.B, d.T, d.N
-    x0 = x0.to(dt).contiguous().clone()          # the kernel moves its z component onto the terrain: returned, not written in place
-    with torch.cuda.device(dev):      # (the policy queries read the CU count of the CURRENT device)
-        Np = _lib.lib().mf_rollout_force_stride(C.byref(d))
-        # the component-parallel kernels' per-step record for the backward (MfRolloutFwdBufs.rec), where the library keeps one
-        nrec = int(_lib.lib().mf_rollout_record_bytes(C.byref(d))) // 4 if (save_for_bwd and dt == torch.float32) else 0
-    d.force_stride = Np
-    new = lambda *tail: torch.empty(T, B, *tail, dtype=dt, device=dev)  # noqa: E731
-    Xs, Xds, Rs, Om, Fs, Ff = new(3), new(3), new(3, 3), new(3), new(Np, 3), new(Np, 3)
-    Xraw = new(3) if save_for_bwd else torch.empty(0, dtype=dt, device=dev)
-    rec = torch.empty(nrec, dtype=dt, device=dev)
-    ts = _time_grid(consts, T, dt, dev)
-    bufs = _lib.MfRolloutFwdBufs(z=_lib.ptr(zc), mu=_lib.ptr(muc), controls=_lib.ptr(cc), ts=_lib.ptr(ts), points=_lib.ptr(pc),
-                                 part=_lib.ptr(part), x0=_lib.ptr(x0), xd0=_lib.ptr(xd0.to(dt).contiguous()), R0=_lib.ptr(R0.to(dt).contiguous()),
-                                 w0=_lib.ptr(w0.to(dt).contiguous()), Xs=_lib.ptr(Xs), Xds=_lib.ptr(Xds), Rs=_lib.ptr(Rs), Omegas=_lib.ptr(Om),
-                                 Fs=_lib.ptr(Fs), Ff=_lib.ptr(Ff), Xraw=_lib.ptr(Xraw) if save_for_bwd else None,
-                                 rec=_lib.ptr(rec) if nrec else None)
-    with torch.cuda.device(dev), _timing.timed('rollout_fwd_kernel', dev):
-        _lib.check(getattr(_lib.lib(), 'mf_rollout_fwd_' + _sfx(dt))(C.byref(d), C.byref(bufs), _stream(dev)), 'mf_rollout_fwd')
+    dt = z.dtype
+    d, zc, muc, cc, pc, part, (x0, xd0, R0, w0), ts = _prep(z, mu, controls, pts, part_id, Iinv, consts, integrator, (x0, xd0, R0, w0))
+    x0 = x0.clone()          # the kernel moves its z component onto the terrain: returned, not written in place
+    with torch.cuda.device(z.device):      # (the policy queries read the CU count of the CURRENT device)
+        # the component-parallel kernels' per-step record for the backward (MfRolloutFwdBufs.rec), where the library keeps one: float32
+        f = rl.launch_forward(d, zc, muc, cc, ts, pc, part, (x0, xd0, R0, w0), want_xraw=save_for_bwd,
+                              want_rec=save_for_bwd and dt == torch.float32)
     tr = lambda t: t.transpose(0, 1)  # noqa: E731
-    return tr(Xs), tr(Xds), tr(Rs), tr(Om), tr(Fs[:, :, :N]), tr(Ff[:, :, :N]), (tr(Xraw) if save_for_bwd else Xraw), x0, rec
+    empty = lambda: torch.empty(0, dtype=dt, device=z.device)  # noqa: E731
+    return (tr(f.Xs), tr(f.Xds), tr(f.Rs), tr(f.Om), tr(f.Fs[:, :, :d.N]), tr(f.Ff[:, :, :d.N]), (tr(f.Xraw) if save_for_bwd else empty()), x0,
+            empty() if f.rec is None else f.rec)
 
 
 @torch.library.impl(_L, 'dphys_rollout_bwd', 'CUDA')
 def _rollout_bwd(z, mu, controls, x_init, xd0, R0, w0, pts, part_id, Iinv, consts, integrator, Xraw, Xds, Rs, Om, rec, gXs, gXds, gRs, gOm, gFs, gFf):
-    dev, dt = z.device, z.dtype
-    zc, muc, cc, pc, part = _prep(z, mu, controls, pts, part_id, (('x_init', x_init), ('xd0', xd0), ('R0', R0), ('w0', w0)))
-    d = _rollout_desc(zc, cc, pc, Iinv, consts, integrator)
-    if dt == torch.float64:
-        d.math_mode = _lib.MF_MATH_EXACT
-    B = d.B
-    tm = lambda t: None if t is None else t.to(dt).transpose(0, 1).contiguous()  # noqa: E731    ([B,T,..] -> time-major rows)
-    saved = [tm(t) for t in (Xraw, Xds, Rs, Om)]
-    ups = [tm(t) for t in (gXs, gXds, gRs, gOm, gFs, gFf)]
+    dt = z.dtype
+    d, zc, muc, cc, pc, part, state, ts = _prep(z, mu, controls, pts, part_id, Iinv, consts, integrator, (x_init, xd0, R0, w0))
+    saved = [t.to(dt).transpose(0, 1).contiguous() for t in (Xraw, Xds, Rs, Om)]      # ([B,T,..] -> time-major rows)
     if d.map_shared:
-        copies = grad_copies_for(B, int(d.N))
-        d.grad_copies = copies
-        n_maps = 2 if muc is not None else 1
-        pool = grad_pool(_POOL_OWNER, n_maps, copies, zc[0].numel(), dt, dev)
-        maps = pool.buf[:n_maps * copies * zc[0].numel()].view((n_maps, copies) + tuple(zc.shape[1:]))
-        gz, gmu, zero_row = maps[0], (maps[1] if muc is not None else None), pool.buf[-16:]
-    else:
-        gz, gmu = torch.zeros_like(zc), (torch.zeros_like(muc) if muc is not None else None)
-        zero_row = torch.zeros(16, dtype=dt, device=dev)
-    gcontrols = torch.empty_like(cc)
-    gx0, gxd0, gR0, gw0 = (torch.empty(B, 3, dtype=dt, device=dev), torch.empty(B, 3, dtype=dt, device=dev),
-                           torch.empty(B, 3, 3, dtype=dt, device=dev), torch.empty(B, 3, dtype=dt, device=dev))
-    ts = _time_grid(consts, d.T, dt, dev)
-    bufs = _lib.MfRolloutBwdBufs(
-        z=_lib.ptr(zc), mu=_lib.ptr(muc), controls=_lib.ptr(cc), ts=_lib.ptr(ts), points=_lib.ptr(pc), part=_lib.ptr(part),
-        x_init=_lib.ptr(x_init.to(dt).contiguous()), xd0=_lib.ptr(xd0.to(dt).contiguous()), R0=_lib.ptr(R0.to(dt).contiguous()),
-        w0=_lib.ptr(w0.to(dt).contiguous()), Xraw=_lib.ptr(saved[0]), Xds=_lib.ptr(saved[1]), Rs=_lib.ptr(saved[2]), Omegas=_lib.ptr(saved[3]),
-        gXs=_lib.ptr(ups[0]), gXds=_lib.ptr(ups[1]), gRs=_lib.ptr(ups[2]), gOmegas=_lib.ptr(ups[3]), gFs=_lib.ptr(ups[4]), gFf=_lib.ptr(ups[5]),
-        zeros=_lib.ptr(zero_row), gz=_lib.ptr(gz), gmu=_lib.ptr(gmu), gcontrols=_lib.ptr(gcontrols), gx0=_lib.ptr(gx0), gxd0=_lib.ptr(gxd0),
-        gR0=_lib.ptr(gR0), gw0=_lib.ptr(gw0), rec=_lib.ptr(rec) if rec.numel() else None)
-    with torch.cuda.device(dev), _timing.timed('rollout_bwd_kernel', dev):
-        _lib.check(getattr(_lib.lib(), 'mf_rollout_bwd_' + _sfx(dt))(C.byref(d), C.byref(bufs), _stream(dev)), 'mf_rollout_bwd')
-    if d.map_shared:
-        summed = pool.reduce(zc.shape[1:])
-        gz = summed[0].unsqueeze(0)
-        gmu = summed[1].unsqueeze(0) if muc is not None else None
-    # a map that came in as ONE shared map next to a per-rollout one was expanded in _prep: its gradient is the sum over the rollouts
-    if gz.shape[0] != z.shape[0]:
-        gz = gz.sum(0, keepdim=True)
-    if gmu is not None and gmu.shape[0] != mu.shape[0]:
-        gmu = gmu.sum(0, keepdim=True)
-    if gmu is None:
-        gmu = torch.zeros(0, dtype=dt, device=dev)
-    return gz, gmu, gcontrols, gx0, gxd0, gR0, gw0
+        d.grad_copies = rl.grad_copies_for(d.B, d.N)
+    with torch.cuda.device(z.device):
+        g = rl.launch_backward(d, zc, muc, cc, ts, pc, part, state, saved, (gXs, gXds, gRs, gOm, gFs, gFf), pool_owner=_POOL_OWNER,
+                               rec=rec if rec.numel() else None)
+    # [1,H,W] for ONE shared map; a map that came in as one shared map next to a per-rollout one was expanded: its gradient is the sum over the rollouts
+    to_input = lambda g_, m: g_.unsqueeze(0) if g_.dim() == 2 else (g_.sum(0, keepdim=True) if g_.shape[0] != m.shape[0] else g_)  # noqa: E731
+    gmu = to_input(g.gmu, mu) if g.gmu is not None else torch.zeros(0, dtype=dt, device=z.device)
+    return to_input(g.gz, z), gmu, g.gcontrols, g.gx0, g.gxd0, g.gR0, g.gw0
 
 
 def _rollout_setup(ctx, inputs, output):

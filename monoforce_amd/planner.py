@@ -103,11 +103,7 @@ class TrajectoryShooter:
             return dict(controls=controls, Xs=out['Xs'], Rs=out['Rs'], pose_steps=out['pose_steps'], costs=costs,
                         best=int(torch.argmin(costs)))
         need_forces = self.cost == 'force'
-        old = self.dp.return_forces
-        self.dp.return_forces = need_forces          # inclination cost only needs the states: states-only kernel
-        try:
-            (Xs, Xds, Rs, Om), (Fs, Ff) = self.dp(z, controls, state=state, friction=mu)
-        finally:
-            self.dp.return_forces = old
+        # (the inclination cost only needs the states: states-only kernel)
+        (Xs, Xds, Rs, Om), (Fs, Ff) = self.dp(z, controls, state=state, friction=mu, _want_forces=need_forces)
         costs = force_path_cost(Fs) if need_forces else inclination_path_cost(Rs)
         return dict(controls=controls, Xs=Xs, Rs=Rs, costs=costs, best=int(torch.argmin(costs)))

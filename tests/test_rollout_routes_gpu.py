@@ -192,7 +192,109 @@ PY_CASES = {
     'py_loss2_value_in_backward': dict(B=16384, value_in_backward=True),
     'py_costs': dict(B=64, costs=True),
     'py_costs_zmu': dict(B=16384, costs=True),
+    # every other entry point of the Python layer (`entry`), with what crossed the C ABI: the descriptor and the non-NULL buffers of each
+    # launch, the gradient pool's copies, whether a record was passed
+    # (recorded with the library code of commit ab3e796, before monoforce_amd/rollout_launch.py existed: they pin that refactor)
+    'py_mod_all': dict(entry='module'),
+    'py_mod_mixed_maps': dict(entry='module', B=8, maps='mixed'),
+    'py_mod_expand8': dict(entry='module', B=8, maps='expand'),
+    'py_mod_expand6': dict(entry='module', B=6, maps='expand'),
+    'py_mod_xs_saturated': dict(entry='module', B=16384, up='xs', kw=dict(return_forces=False)),
+    'py_mod_contiguous': dict(entry='module', kw=dict(contiguous_outputs=True)),
+    'py_mod_precise': dict(entry='module', kw=dict(precise=True)),
+    'py_mod_f64_cp': dict(entry='module', f64=True, up='states', kw=dict(points_per_lane=COMPONENT, return_forces=False)),
+    'py_mod_default_state': dict(entry='module', up=None, controls='time_constant'),
+    'py_ops_shared': dict(entry='ops'),
+    'py_ops_per_rollout': dict(entry='ops', maps='per_rollout'),
+    'py_ops_f64': dict(entry='ops', f64=True),
+    'py_planner_no_forces': dict(entry='planner', cost='inclination'),
+    'py_planner_forces': dict(entry='planner', cost='force'),
 }
+
+
+class _AbiSpy:
+    """Stands in for mf_rollout_fwd_* / mf_rollout_bwd_* on the loaded library while one entry point runs: notes, per launch, the
+    descriptor, the names of the non-NULL buffers and -- on the launching thread, the backward's is autograd's -- mf_last_launch()."""
+
+    def __init__(self, L):
+        self.L, self.seen, self.orig = L, {}, {}
+
+    def __enter__(self):
+        for way in ('fwd', 'bwd'):
+            for sfx in ('f32', 'f64'):
+                name = f'mf_rollout_{way}_{sfx}'
+                self.orig[name] = getattr(self.L, name)
+                setattr(self.L, name, self._wrap(way, self.orig[name]))
+        return self
+
+    def __exit__(self, *exc):
+        for name, fn in self.orig.items():
+            setattr(self.L, name, fn)
+
+    def _wrap(self, way, fn):
+        def call(desc, bufs, stream):
+            rc = fn(desc, bufs, stream)
+            d, b = desc._obj, bufs._obj
+            r9 = lambda v: float('%.9g' % v) if isinstance(v, float) else v  # noqa: E731  (Iinv comes from a host LAPACK inverse: not to the last bit)
+            fields = {n: ([r9(v) for v in getattr(d, n)] if n in ('Iinv', 'joint_xyz') else r9(getattr(d, n))) for n, _ in d._fields_}
+            assert way not in self.seen, f'two {way} launches in one case'
+            self.seen[way] = dict(launch=self.L.mf_last_launch().decode().split(' launches=')[0], rc=rc,
+                                  desc={n: v for n, v in fields.items() if v and (not isinstance(v, list) or any(v))},
+                                  bufs=sorted(n for n, _ in b._fields_ if getattr(b, n)))
+            return rc
+        return call
+
+
+def run_entry_case(c):
+    """One entry point of the Python layer other than the fused loss and the path costs: what its forward and backward launch (kernel,
+    descriptor, non-NULL buffers), the timed names, the gradient pool's copies and whether a record was passed."""
+    import torch
+    from monoforce_amd import _lib, _timing, ops, synthetic as syn
+    from monoforce_amd.planner import TrajectoryShooter
+    from tests.test_rollout_gpu import DEV, make_dphysics
+    B, T = c['B'], 20
+    dt = torch.float64 if c.get('f64') else torch.float32
+    pts, masks = syn.robot_points_4()
+    dp = make_dphysics(pts, masks, 1, 0.1, 3.2, **c.get('kw', {}))
+    dp.dphys_cfg.traj_sim_time = 5.0
+    z1 = syn.bump_terrain(syn.bump_params(5), 3.2, 0.1, dt).to(DEV).unsqueeze(0).requires_grad_(True)
+    mu1 = syn.wave_friction(3.2, 0.1, dtype=dt).to(DEV).unsqueeze(0).requires_grad_(True)
+    maps = c.get('maps', 'shared')
+    z = {'shared': z1, 'expand': z1.expand(B, -1, -1)}.get(maps)
+    if z is None:       # 'mixed' (z per rollout, mu shared) and 'per_rollout': a [B,H,W] leaf
+        z = z1.detach().repeat(B, 1, 1).requires_grad_(True)
+    mu = mu1.detach().repeat(B, 1, 1).requires_grad_(True) if maps == 'per_rollout' else mu1
+    ctrl = syn.const_controls(B, T, seed=2, dtype=dt).to(DEV)
+    if c.get('controls') == 'time_constant':
+        ctrl = ctrl[:, 0][:, None].expand(B, T, 2)
+    elif c['entry'] != 'planner':
+        ctrl.requires_grad_(True)
+    up = c.get('up', 'all')
+    pools = None
+    _timing.start()
+    with _AbiSpy(_lib.lib()) as spy:
+        if c['entry'] == 'planner':
+            TrajectoryShooter(dp, cost=c['cost'], fused=False).shoot(z.detach(), friction=mu.detach(), controls=ctrl)
+        elif up is None:
+            with torch.no_grad():
+                dp(z.detach(), ctrl, friction=mu.detach())
+        else:
+            if c['entry'] == 'ops':
+                eye = torch.eye(3, dtype=dt, device=DEV).repeat(B, 1, 1)
+                state = tuple(torch.zeros(B, 3, dtype=dt, device=DEV) for _ in range(2)) + (eye, torch.zeros(B, 3, dtype=dt, device=DEV))
+                states, forces = ops.rollout(dp, z, ctrl, state, friction=mu)
+                pools = ops._POOL_OWNER
+            else:
+                states, forces = dp(z, ctrl, friction=mu)
+                pools = dp
+            outs = {'all': list(states) + list(forces), 'states': list(states), 'xs': list(states)[:1]}[up]
+            sum(o.sum() for o in outs).backward()
+        torch.cuda.synchronize()
+    out = dict(timed=sorted(_timing.stop()), **spy.seen)
+    out['rec'] = 'rec' in out['fwd']['bufs']
+    if pools is not None and out['bwd']['desc'].get('map_shared'):
+        out['copies'] = list(pools._grad_pools.values())[-1].copies       # (the pool used last is the dict's last entry)
+    return out
 
 
 def run_py_case(spec):
@@ -202,6 +304,8 @@ def run_py_case(spec):
     from tests.test_rollout_gpu import DEV, make_dphysics
     c = dict(B=64, integ=1, value_in_backward=False, costs=False)
     c.update(spec)
+    if 'entry' in c:
+        return run_entry_case(c)
     B, T = c['B'], 20
     pts, masks = syn.robot_points_4()
     dp = make_dphysics(pts, masks, c['integ'], 0.1, 3.2)

@@ -1,4 +1,4 @@
-"""Backward of large bodies vs the number of private gradient copies of a shared map (dphysics_bwd.GRAD_COPIES): AB_B, AB_N."""
+"""Backward of large bodies vs the number of private gradient copies of a shared map (rollout_launch.GRAD_COPIES): AB_B, AB_N."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
