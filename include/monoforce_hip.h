@@ -474,6 +474,42 @@ long long mf_mppi_scratch_bytes(const MfMppiDesc* desc);
 int mf_mppi_update_f32(const MfMppiDesc* desc, const float* costs, const float* controls, const float* nominal_in, float* weights,
                        float* nominal_out, int32_t* best, int32_t* n_valid, void* scratch, long long scratch_bytes, void* hip_stream);
 
+/* ---- Planner costs from the kept poses of a path-cost rollout: a 2-D cost map under the footprint, and path following ---------------
+ * (no reference equivalent).  Xs / Rs are the decimated poses exactly as DPhysics.rollout_costs hands them out (sink-shifted Xs, the
+ * drifting R of the default integrator), read in place through the strides.  For rollout b, kept pose p, footprint point n:
+ *   q = Xs[b,p,0:2] + Rs[b,p,0:2,:] . points[n];   u = (q.x + d_max) / grid_res, v = (q.y + d_max) / grid_res
+ *   the point is on the map iff 0 <= u <= H-1 and 0 <= v <= W-1 (a NaN is off the map).  Off the map s = off_map; on it
+ *   ix = min(floor(u), H-2), iy = min(floor(v), W-2), fx = u - ix, fy = v - iy,
+ *   s = (1-fx)(1-fy) m[ix][iy] + fx(1-fy) m[ix+1][iy] + (1-fx) fy m[ix][iy+1] + fx fy m[ix+1][iy+1],   m[i][j] = cost_map[i*W + j]
+ * cost_map[i][j] sits on node (i, j) of z_grid (the node interpolate_grid calls c): first axis x, the same d_max and grid_res.  The
+ * blend is the CORRECT bilinear one, deliberately not interpolate_grid's bug-for-bug form (swapped fraction weights, discontinuous
+ * across cell edges): a cost map is no reference quantity, so there is no bug to stay compatible with, and a continuous sample keeps
+ * float32 from flipping costs at cell edges.
+ *   map term   f[b,p] = max_n s;  map[b] = (1/Tp) sum_p f[b,p];  if any sample of the rollout is NOT < lethal, map[b] = +inf and the
+ *              cost takes +inf for it whatever w_map is (never 0 x inf).  NaN cells, and NaN rotations under an infinite off_map, end here.
+ *   path term  (P > 0) d[b,p] = distance of Xs[b,p,0:2] to the polyline path[0..P-1]: the minimum over the P-1 segments, the projection
+ *              parameter clamped to [0,1], a zero-length segment is its point, P = 1 is the distance to that point;
+ *              xtrack[b] = (1/Tp) sum_p d[b,p]   (a NaN position gives a NaN term)
+ *   costs[b] = (base_costs ? base_costs[b] : 0) + w_map map[b] + w_path xtrack[b];   terms[b] = (map[b], xtrack[b])
+ * A NULL cost_map requires w_map == 0: its term is exactly 0 and is not evaluated; P == 0 requires w_path == 0 and a NULL path, likewise.
+ * A given cost_map is always evaluated (the lethal rule holds with w_map == 0).  One launch; no float atomics, a fixed summation order
+ * for a given (B, Tp, N): bit-identical from call to call and between the rollout's time-major views and a contiguous copy; never
+ * synchronises, everything is read on the device (capturable); costs may alias base_costs.  Limits: N <= 1024, P <= 256,
+ * H * W and the index range of the pose rows below 2^31. */
+typedef struct MfPoseCostDesc {
+  int32_t B, Tp, N, P;            /* rollouts, kept poses per rollout, footprint points, path vertices (0: no path term) */
+  int32_t H, W;                   /* cost map cells */
+  int64_t x_stride_b, x_stride_t; /* Xs[b*sb + t*st + c], c < 3 (elements) */
+  int64_t r_stride_b, r_stride_t; /* Rs[b*sb + t*st + 3*i + j] */
+  float grid_res, d_max;
+  float lethal;                   /* a sample that is NOT < lethal makes the rollout's cost +inf; +inf: no such rule */
+  float off_map;                  /* sample value of a footprint point off the map (may be +inf) */
+  float w_map, w_path;
+} MfPoseCostDesc;
+int mf_pose_costs_f32(const MfPoseCostDesc* desc, const float* Xs, const float* Rs, const float* points /* [N][3] body frame */,
+                      const float* cost_map /* [H][W] or NULL */, const float* path /* [P][2] or NULL iff P == 0 */,
+                      const float* base_costs /* [B] or NULL */, float* costs /* [B] */, float* terms /* [B][2] or NULL */, void* hip_stream);
+
 /* Text of the calling thread's last error ("" if none).  THREAD-LOCAL: host threads driving different streams each read the message
  * of their own failed call (the reference raises a Python exception in the calling thread, dphysics.py:575,579 asserts). */
 const char* mf_last_error(void);

@@ -80,11 +80,17 @@ class MfMppiDesc(C.Structure):
                 ('w_incl', C.c_float), ('w_force', C.c_float), ('w_goal', C.c_float), ('lam', C.c_float)]
 
 
+class MfPoseCostDesc(C.Structure):
+    _fields_ = [('B', C.c_int32), ('Tp', C.c_int32), ('N', C.c_int32), ('P', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
+                ('x_stride_b', C.c_int64), ('x_stride_t', C.c_int64), ('r_stride_b', C.c_int64), ('r_stride_t', C.c_int64),
+                ('grid_res', C.c_float), ('d_max', C.c_float), ('lethal', C.c_float), ('off_map', C.c_float), ('w_map', C.c_float), ('w_path', C.c_float)]
+
+
 # every symbol include/monoforce_hip.h declares; tests check the library exports all of them
 SYMBOLS = ['mf_rollout_force_stride', 'mf_rollout_fwd_f32', 'mf_rollout_fwd_f64', 'mf_rollout_default_state_f32', 'mf_rollout_default_state_f64', 'mf_rollout_bwd_f32', 'mf_rollout_bwd_f64', 'mf_rollout_bwd_wants_gcontrols', 'mf_rollout_record_bytes', 'mf_rollout_record_bytes_f64', 'mf_rollout_fwd_stages_zmu', 'mf_rollout_loss_fusable', 'mf_rollout_bwd_window', 'mf_bev_splat_workspace_bytes', 'mf_bev_splat_prepare', 'mf_bev_splat_prepare_cameras', 'mf_bev_splat_prepare_rig',
            'mf_bev_splat_fwd_f32', 'mf_bev_splat_fwd_f64', 'mf_bev_splat_bwd_f32', 'mf_bev_splat_bwd_f64',
            'mf_bev_lift_splat_fwd_f32', 'mf_bev_lift_splat_fwd_f64', 'mf_bev_lift_splat_bwd_f32', 'mf_bev_lift_splat_bwd_f64',
-           'mf_physics_loss_fwd_f32', 'mf_physics_loss_fwd_f64', 'mf_physics_loss_bwd_f32', 'mf_physics_loss_bwd_f64', 'mf_physics_loss_value_f32', 'mf_physics_loss_value_f64', 'mf_nearest_steps_f32', 'mf_nearest_steps_f64', 'mf_reduce_grad_copies_f32', 'mf_reduce_grad_copies_f64', 'mf_estimate_heightmap_f32', 'mf_interpolate_grid_f32', 'mf_interpolate_grid_f64', 'mf_terrain_stage_fwd_f32', 'mf_terrain_stage_bwd_f32', 'mf_mppi_perturb_f32', 'mf_path_costs_f32', 'mf_mppi_scratch_bytes', 'mf_mppi_update_f32', 'mf_last_error', 'mf_last_launch', 'mf_version', 'mf_sizeof']
+           'mf_physics_loss_fwd_f32', 'mf_physics_loss_fwd_f64', 'mf_physics_loss_bwd_f32', 'mf_physics_loss_bwd_f64', 'mf_physics_loss_value_f32', 'mf_physics_loss_value_f64', 'mf_nearest_steps_f32', 'mf_nearest_steps_f64', 'mf_reduce_grad_copies_f32', 'mf_reduce_grad_copies_f64', 'mf_estimate_heightmap_f32', 'mf_interpolate_grid_f32', 'mf_interpolate_grid_f64', 'mf_terrain_stage_fwd_f32', 'mf_terrain_stage_bwd_f32', 'mf_mppi_perturb_f32', 'mf_path_costs_f32', 'mf_mppi_scratch_bytes', 'mf_mppi_update_f32', 'mf_pose_costs_f32', 'mf_last_error', 'mf_last_launch', 'mf_version', 'mf_sizeof']
 
 _lib = None
 _lock = threading.Lock()
@@ -109,7 +115,7 @@ def lib():
                 L.mf_last_launch.restype = C.c_char_p
                 for name in SYMBOLS:
                     fn = getattr(L, name)   # AttributeError if the build is stale
-                    if name.startswith(('mf_rollout', 'mf_bev', 'mf_physics', 'mf_estimate', 'mf_terrain', 'mf_reduce', 'mf_interpolate', 'mf_nearest', 'mf_mppi', 'mf_path')):
+                    if name.startswith(('mf_rollout', 'mf_bev', 'mf_physics', 'mf_estimate', 'mf_terrain', 'mf_reduce', 'mf_interpolate', 'mf_nearest', 'mf_mppi', 'mf_path', 'mf_pose')):
                         fn.restype = C.c_int
                 L.mf_bev_splat_workspace_bytes.restype = C.c_size_t
                 L.mf_rollout_record_bytes.restype = C.c_longlong

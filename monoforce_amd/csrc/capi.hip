@@ -69,5 +69,6 @@ extern "C" int mf_sizeof(const char* name) {
   if (!strcmp(name, "MfInterpDesc")) return (int)sizeof(MfInterpDesc);
   if (!strcmp(name, "MfRolloutLoss")) return (int)sizeof(MfRolloutLoss);
   if (!strcmp(name, "MfMppiDesc")) return (int)sizeof(MfMppiDesc);
+  if (!strcmp(name, "MfPoseCostDesc")) return (int)sizeof(MfPoseCostDesc);
   return -1;
 }

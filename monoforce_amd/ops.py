@@ -18,6 +18,8 @@ Schemas (tensors on the GPU, float32 or float64; `Bz` in {1, B}: a [1,H,W] map i
     monoforce::path_costs(Tensor cost_rows, Tensor? force_cost, Tensor x_last, Tensor goal, float[] weights) -> (Tensor costs, Tensor terms)
     monoforce::mppi_update(Tensor costs, Tensor controls, Tensor nominal, float lam)
                                  -> (Tensor nominal, Tensor weights, Tensor best, Tensor n_valid)
+    monoforce::pose_costs(Tensor Xs, Tensor Rs, Tensor points, Tensor? cost_map, Tensor? path, Tensor? base_costs, float grid_res,
+                          float d_max, float lethal, float off_map, float[] weights) -> (Tensor costs, Tensor terms)
 
 `consts` = [mass, gravity, stiffness, damping, grid_res, d_max, dt, omega_max, robot_size_y(, traj_sim_time)]; `part_id[N]` int32
 (index of the last driving mask holding the point, -1 = not driving); `Iinv` [3,3] on the HOST (nine scalars of the launch
@@ -33,6 +35,11 @@ The three MPPI ops (float32, no autograd; monoforce_amd/mppi.py is their consume
 [B,T,4] in any strides whose last axis is dense (the [B,T,4] view `DPhysics.rollout_costs` returns is read in place), `x_last` [B,>=2], `goal`
 [2] on the device, `weights` = (inclination, force, goal) with `force_cost` given exactly when the force weight is non-zero; `best` / `n_valid`
 are int32 [1] on the device.
+
+`pose_costs` (float32, no autograd; monoforce_amd/csrc/pose_costs.hip, formulas in include/monoforce_hip.h at MfPoseCostDesc): `Xs` [B,Tp,3] and
+`Rs` [B,Tp,3,3] are the kept poses of `DPhysics.rollout_costs`, read in place through their strides (the time-major views need no copy);
+`points` [N,3] the footprint in the body frame; `cost_map` [H,W] on the nodes of z_grid; `path` [P,2]; `weights` = (map, path), each 0 when
+its input is None; `costs` [B] = base_costs + w_map map + w_path xtrack, `terms` [B,2] = (map, xtrack).  One launch.
 
 The rollout ops and `DPhysics`'s own autograd function (monoforce_amd/dphysics.py: more options -- articulated bodies, path costs,
 strided controls) launch through the same marshalling (monoforce_amd/rollout_launch.py); `rollout()` / `splat()` below are the
@@ -67,6 +74,8 @@ _L.define('bev_splat_bwd(Tensor grad, Tensor plan, int B, int n_per_sample, int 
 _L.define('mppi_perturb(Tensor nominal, Tensor noise, float[] sigma, float[] lo, float[] hi, bool keep_nominal) -> Tensor')
 _L.define('path_costs(Tensor cost_rows, Tensor? force_cost, Tensor x_last, Tensor goal, float[] weights) -> (Tensor, Tensor)')
 _L.define('mppi_update(Tensor costs, Tensor controls, Tensor nominal, float lam) -> (Tensor, Tensor, Tensor, Tensor)')
+_L.define('pose_costs(Tensor Xs, Tensor Rs, Tensor points, Tensor? cost_map, Tensor? path, Tensor? base_costs, float grid_res, float d_max, '
+          'float lethal, float off_map, float[] weights) -> (Tensor, Tensor)')
 
 
 def _sfx(dtype):
@@ -345,6 +354,59 @@ def _path_costs_fake(cost_rows, force_cost, x_last, goal, weights):
 def _mppi_update_fake(costs, controls, nominal, lam):
     B = controls.shape[0]
     return (nominal.new_empty(nominal.shape), costs.new_empty(B), costs.new_empty(1, dtype=torch.int32), costs.new_empty(1, dtype=torch.int32))
+
+
+# ---- planner costs from the kept poses -------------------------------------------------------------------------------------------
+def footprint_points(dphysics):
+    """The default footprint of the cost-map term: the DPhysics robot points [N,3], float32 on its device (cached on the module)."""
+    key = ('footprint_f32', str(dphysics.device))
+    if key not in dphysics._cache:
+        dphysics._cache[key] = dphysics.dphys_cfg.robot_points.detach().to(device=dphysics.device, dtype=torch.float32).reshape(-1, 3).contiguous()
+    return dphysics._cache[key]
+
+
+def pose_costs_into(Xs, Rs, points, cost_map, path, base_costs, grid_res, d_max, lethal, off_map, weights, out):
+    """`torch.ops.monoforce.pose_costs` writing the costs into `out` [B] (which may be `base_costs` itself); returns (out, terms)."""
+    x, r = _f32(Xs, 'Xs'), _f32(Rs, 'Rs')
+    assert x.dim() == 3 and x.shape[2] == 3 and tuple(r.shape) == (x.shape[0], x.shape[1], 3, 3), \
+        f'Xs must be [B,Tp,3] and Rs [B,Tp,3,3], got {tuple(x.shape)} and {tuple(r.shape)}'
+    B, Tp = x.shape[:2]
+    if x.stride(2) != 1:
+        x = x.contiguous()
+    if r.stride(3) != 1 or r.stride(2) != 3:
+        r = r.contiguous()
+    pts = _f32(points, 'points').contiguous()
+    assert pts.dim() == 2 and pts.shape[1] == 3, f'points must be [N,3], got {tuple(pts.shape)}'
+    assert len(weights) == 2, 'weights = (map, path)'
+    cm = None if cost_map is None else _f32(cost_map, 'cost_map').contiguous()
+    assert cm is None or cm.dim() == 2, 'cost_map must be [H,W]'
+    pa = None if path is None else _f32(path, 'path').contiguous()
+    assert pa is None or (pa.dim() == 2 and pa.shape[1] == 2), 'path must be [P,2]'
+    base = None if base_costs is None else _f32(base_costs, 'base_costs')
+    assert base is None or (tuple(base.shape) == (B,) and base.is_contiguous()), 'base_costs must be a dense [B]'
+    assert tuple(out.shape) == (B,) and out.is_contiguous() and out.dtype == torch.float32 and out.device == x.device
+    H, W = (2, 2) if cm is None else cm.shape
+    d = _lib.MfPoseCostDesc(B=B, Tp=Tp, N=pts.shape[0], P=0 if pa is None else pa.shape[0], H=H, W=W,
+                            x_stride_b=x.stride(0), x_stride_t=x.stride(1), r_stride_b=r.stride(0), r_stride_t=r.stride(1),
+                            grid_res=float(grid_res), d_max=float(d_max), lethal=float(lethal), off_map=float(off_map),
+                            w_map=float(weights[0]), w_path=float(weights[1]))
+    terms = torch.empty(B, 2, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timing.timed('pose_costs_kernel', x.device):
+        _lib.check(_lib.lib().mf_pose_costs_f32(C.byref(d), _lib.ptr(x), _lib.ptr(r), _lib.ptr(pts), _lib.ptr(cm), _lib.ptr(pa), _lib.ptr(base),
+                                                _lib.ptr(out), _lib.ptr(terms), _stream(x.device)), 'mf_pose_costs')
+    return out, terms
+
+
+@torch.library.impl(_L, 'pose_costs', 'CUDA')
+def _pose_costs(Xs, Rs, points, cost_map, path, base_costs, grid_res, d_max, lethal, off_map, weights):
+    return pose_costs_into(Xs, Rs, points, cost_map, path, base_costs, grid_res, d_max, lethal, off_map, weights,
+                           torch.empty(Xs.shape[0], dtype=torch.float32, device=Xs.device))
+
+
+@torch.library.register_fake('monoforce::pose_costs', lib=_L)
+def _pose_costs_fake(Xs, Rs, points, cost_map, path, base_costs, grid_res, d_max, lethal, off_map, weights):
+    B = Xs.shape[0]
+    return Xs.new_empty(B), Xs.new_empty(B, 2)
 
 
 # ---- functional entries ------------------------------------------------------------------------------------------------------

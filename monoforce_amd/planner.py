@@ -12,7 +12,9 @@ paths, pick the cheapest -- the device-side part of the reference's planning nod
 All rollouts share ONE height/friction map (the rollout kernels' shared-map path), so thousands of samples cost one
 512 KiB map read.  By default the rollout runs in the kernel's path-cost mode (`DPhysics.rollout_costs`): per step it writes
 one 16-byte cost row (the last row of R and the std over the contact points of |F_spring|) and keeps every
-`pose_stride`-th pose instead of the full 180-byte output row; `fused=False` uses the full outputs.
+`pose_stride`-th pose instead of the full 180-byte output row; `fused=False` uses the full outputs.  On the fused route
+`shoot(cost_map=..., path=...)` adds a 2-D cost map sampled under the footprint and the distance to a path, scored from the
+kept poses by one more launch (`torch.ops.monoforce.pose_costs`).
 """
 import torch
 
@@ -72,7 +74,10 @@ def nearest_rotation_row2(Rs, iters=3):
 
 
 class TrajectoryShooter:
-    def __init__(self, dphysics, n_trajs=None, cost='inclination', fused=True, pose_stride=None):
+    def __init__(self, dphysics, n_trajs=None, cost='inclination', fused=True, pose_stride=None, map_weight=0.0, path_weight=0.0,
+                 lethal=float('inf'), off_map=float('inf')):
+        """`map_weight`, `path_weight`: weights of the cost-map and path terms of `shoot(cost_map=..., path=...)`; a footprint sample
+        that is not < `lethal` makes its rollout's cost +inf, a footprint point off the map samples `off_map`."""
         assert cost in ('inclination', 'force')
         self.dp = dphysics
         self.cfg = dphysics.dphys_cfg
@@ -80,13 +85,24 @@ class TrajectoryShooter:
         self.cost = cost
         self.fused = fused and not dphysics.precise      # path-cost kernel: float32 fast math
         self.pose_stride = pose_stride
+        self.pose_weights = (float(map_weight), float(path_weight))
+        self.lethal, self.off_map = float(lethal), float(off_map)
 
     @torch.no_grad()
-    def shoot(self, z_grid, friction=None, pose0=None, controls=None, generator=None):
-        """z_grid [H,W] (or [1,H,W]); pose0 optional 4x4 start pose shared by all samples.
+    def shoot(self, z_grid, friction=None, pose0=None, controls=None, generator=None, cost_map=None, path=None):
+        """z_grid [H,W] (or [1,H,W]); pose0 optional 4x4 start pose shared by all samples; cost_map [H,W] (on the nodes of z_grid) and
+        path [P,2]: optional float32 device tensors, fused route only -- the shooter's cost goes in as the base cost, `costs` and `best`
+        are of the sum, and the dict gains `pose_terms` [B,2] = (map, cross-track).
         Returns dict(controls, Xs, Rs, costs, best) -- `best` is the index of the cheapest path; with the fused path-cost
         kernel Xs / Rs hold every `pose_stride`-th pose (+ the final one) and `pose_steps` their step indices."""
         dev = z_grid.device
+        scored = cost_map is not None or path is not None
+        if scored and not (self.fused and z_grid.dtype == torch.float32):
+            raise ValueError('TrajectoryShooter.shoot: cost_map / path are scored from the kept poses of the fused float32 route '
+                             '(fused=True, DPhysics(precise=False)); this shooter uses the full outputs')
+        for name, t, wt in (('cost_map', cost_map, self.pose_weights[0]), ('path', path, self.pose_weights[1])):
+            if t is None and wt != 0:
+                raise ValueError(f'TrajectoryShooter.shoot: {name.split("_")[-1]}_weight is {wt} but no {name} was given')
         if controls is None:
             controls = sample_controls(self.n_trajs, self.cfg, dev, generator)
         B = controls.shape[0]
@@ -100,6 +116,13 @@ class TrajectoryShooter:
             out = self.dp.rollout_costs(z, controls, state=state, friction=mu, pose_stride=self.pose_stride,
                                         project=self.cost == 'inclination')
             costs = out['force_cost'] if self.cost == 'force' else costs_from_rows(out['cost_rows'], self.cost)
+            if scored:
+                from . import ops
+                costs, pose_terms = torch.ops.monoforce.pose_costs(out['Xs'], out['Rs'], ops.footprint_points(self.dp), cost_map, path, costs.contiguous(),
+                                                                   float(self.cfg.grid_res), float(self.cfg.d_max), self.lethal, self.off_map,
+                                                                   list(self.pose_weights))
+                return dict(controls=controls, Xs=out['Xs'], Rs=out['Rs'], pose_steps=out['pose_steps'], costs=costs, pose_terms=pose_terms,
+                            best=int(torch.argmin(costs)))
             return dict(controls=controls, Xs=out['Xs'], Rs=out['Rs'], pose_steps=out['pose_steps'], costs=costs,
                         best=int(torch.argmin(costs)))
         need_forces = self.cost == 'force'
