@@ -17,6 +17,8 @@
  *   mf_bev_lift_splat_*  the same with the lift of lss.py:63-71 (depth distribution x context features) fused in
  *   mf_physics_loss_*  losses.py:102-127 physics_loss (position term) and its gradient, on the nearest-time-stamp
  *                      subset of the predicted poses
+ *   mf_pose_loss_*     losses.py:102-138 physics_loss(rotation_loss=True): the position term and the geodesic rotation term
+ *                      (rotation_difference, :48-65) in one launch, and their gradients in another
  *   mf_bev_splat_prepare_cameras  the voxel plan straight from the camera models: LiftSplatShoot.get_geometry()
  *                      (lss.py:204-224) evaluated inside the key pass
  */
@@ -386,6 +388,43 @@ int mf_nearest_steps_f64(int32_t B, int32_t T1, int32_t T2, const double* pred_t
  * of `zero_count` scalars cleared by the same launch -- the gXs a later mf_physics_loss_bwd_* scatters into. */
 int mf_physics_loss_value_f32(const MfLossDesc* desc, const float* Xs, const float* Xgt, const float* gt_ts, const int32_t* nearest, float* partial, uint32_t* ticket, float* loss, float* zero_fill, long long zero_count, void* hip_stream);
 int mf_physics_loss_value_f64(const MfLossDesc* desc, const double* Xs, const double* Xgt, const double* gt_ts, const int32_t* nearest, double* partial, uint32_t* ticket, double* loss, double* zero_fill, long long zero_count, void* hip_stream);
+/* ---- fused pose loss: physics_loss(..., rotation_loss=True) (losses.py:102-138, rotation_difference :48-65) ----------------------
+ * The call scripts/eval.py:151-153 makes on every batch.  With near = nearest[b,j], w = 1 / (1 + gamma * gt_ts[b,j]):
+ *   loss[0] = mean_{b,j,c} ((Xs[b,near,c] - Xgt[b,j,c]) * w)^2                                   (the mf_physics_loss_* term, same arithmetic)
+ *   loss[1] = mean_{b,j} theta^2 * w,  theta = acos(clip((tr - 1) / 2, -1, 1)),  tr = sum_{r,k} Rs[b,near,r,k] * Rgt[b,j,r,k] = trace(Rp Rg^T)
+ * Xs is addressed as Xs[b*x_stride_b + t*x_stride_t + c], Rs as Rs[b*r_stride_b + t*r_stride_t + 3*r + k] (elements): the rollout's
+ * time-major [T,B,3,3] buffers viewed as [B,T,3,3] and dense [B,T,3,3] tensors work in place.  Xgt [B][T2][3], Rgt [B][T2][3][3],
+ * gt_ts [B][T2], nearest int32 [B][T2] (values in [0, T1)) are dense.  B * T2 must be below 2^31. */
+typedef struct MfPoseLossDesc {
+  int32_t B, T1, T2;            /* rollouts, predicted steps, ground-truth stamps */
+  int32_t reserved;
+  int64_t x_stride_b, x_stride_t;
+  int64_t r_stride_b, r_stride_t;
+  double gamma;
+} MfPoseLossDesc;
+/* losses.py:116-136 (both returned scalars), finished inside the launch like mf_physics_loss_value_*: `partial` holds
+ * 2 * ceil(B*T2/256) scalars of scratch, `ticket` is ONE zero-initialised uint32 the library resets itself (calls ordered on one
+ * stream may share it, also with mf_physics_loss_value_*), loss[0..1] receive the two means, summed in block order (deterministic).
+ * `zero_x` / `zero_r` (each may be NULL with a count of 0): buffers of `zero_*_count` scalars cleared by the same launch -- the gXs /
+ * gRs a later mf_pose_loss_bwd_* scatters into. */
+int mf_pose_loss_value_f32(const MfPoseLossDesc* desc, const float* Xs, const float* Rs, const float* Xgt, const float* Rgt, const float* gt_ts,
+                           const int32_t* nearest, float* partial, uint32_t* ticket, float* loss, float* zero_x, long long zero_x_count,
+                           float* zero_r, long long zero_r_count, void* hip_stream);
+int mf_pose_loss_value_f64(const MfPoseLossDesc* desc, const double* Xs, const double* Rs, const double* Xgt, const double* Rgt, const double* gt_ts,
+                           const int32_t* nearest, double* partial, uint32_t* ticket, double* loss, double* zero_x, long long zero_x_count,
+                           double* zero_r, long long zero_r_count, void* hip_stream);
+/* The autograd backward of losses.py:116-136 with respect to states_pred[0] and states_pred[2] (the gather's index_put_, the matmul,
+ * clip and arccos backward), given the upstream gradients gloss[0..1] of the two scalars.  gXs / gRs have the strides of Xs / Rs and are
+ * ZERO on entry; either may be NULL (that half is skipped), not both.  Stamps of one rollout that share a step add up (float atomics),
+ * a step one stamp has to itself is stored.
+ *   gXs[b,near,c] (+)= gloss[0] * 2 w (Xs w - Xgt w) / (3 B T2)
+ *   gRs[b,near,:] (+)= gloss[1] * w / (B T2) * dtheta2 * Rgt[b,j,:],   dtheta2 = -theta / sqrt((1-c)(1+c)) for -1 < c < 1, else 0
+ * ONE difference from autograd: at c == +-1 exactly (inside the clip range) torch's arccos backward gives 0 * inf = NaN for identical
+ * rotations and inf at exactly pi; here the rotation gradient is 0 there.  For tr outside [-1, 3] both give 0 (clip's mask). */
+int mf_pose_loss_bwd_f32(const MfPoseLossDesc* desc, const float* Xs, const float* Rs, const float* Xgt, const float* Rgt, const float* gt_ts,
+                         const int32_t* nearest, const float* gloss, float* gXs, float* gRs, void* hip_stream);
+int mf_pose_loss_bwd_f64(const MfPoseLossDesc* desc, const double* Xs, const double* Rs, const double* Xgt, const double* Rgt, const double* gt_ts,
+                         const int32_t* nearest, const double* gloss, double* gXs, double* gRs, void* hip_stream);
 /* The reduction that follows a shared-map mf_rollout_bwd_* (MfRolloutDesc.grad_copies private copies of each map gradient,
  * pool = [n_maps][copies][n]):  out[m][i] = sum_c pool[m][c][i], and pool is left ZEROED -- a caller that keeps the pool across
  * steps never fills it again (replaces a zero fill + `maps.sum(1)`, scripts/train.py's optimizer step reads `out`). */

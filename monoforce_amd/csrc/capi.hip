@@ -70,5 +70,6 @@ extern "C" int mf_sizeof(const char* name) {
   if (!strcmp(name, "MfRolloutLoss")) return (int)sizeof(MfRolloutLoss);
   if (!strcmp(name, "MfMppiDesc")) return (int)sizeof(MfMppiDesc);
   if (!strcmp(name, "MfPoseCostDesc")) return (int)sizeof(MfPoseCostDesc);
+  if (!strcmp(name, "MfPoseLossDesc")) return (int)sizeof(MfPoseLossDesc);
   return -1;
 }

@@ -1,12 +1,13 @@
 """Losses that sit directly on top of the rollout / encoder outputs (plain torch; they run on whatever device the
 tensors are on).  Semantics of `/root/reference/monoforce/src/monoforce/losses.py`: `physics_loss` :102-138, `hm_loss`
-:77-99, `total_variation` :68-74.
+:77-99, `total_variation` :68-74, `rotation_difference` :48-65, `translation_difference` :36-45, `slerp` :14-34.
 """
 import torch
 
 _HIP_LOSS = True      # physics_loss on GPU tensors runs on the mf_physics_loss_* kernels (False: the reference's ATen form)
 
-__all__ = ['nearest_steps', 'nearest_steps_hip', 'physics_loss', 'physics_loss_aten', 'physics_loss_fused', 'hm_loss', 'total_variation', 'rotation_difference']
+__all__ = ['nearest_steps', 'nearest_steps_hip', 'physics_loss', 'physics_loss_aten', 'physics_loss_fused', 'hm_loss', 'total_variation', 'rotation_difference',
+           'translation_difference', 'slerp']
 
 
 def total_variation(heightmap):
@@ -73,6 +74,12 @@ def physics_loss(states_pred, states_gt, pred_ts, gt_ts, gamma=0.9, rotation_los
     forward, one scatter launch backward, the index table from `mf_nearest_steps_*`) instead of ~25 ATen launches -- the reference's
     own form (`physics_loss_aten`) costs 0.29 ms of GPU time per call at the BASELINE shape, as much as the rollout's forward and
     half its backward (a sort inside `index_put_`'s backward, two 25.6 M-element temporaries for the argmin).
+    `rotation_loss=True` (scripts/eval.py:151-153) returns `(loss, loss_rot)`, the second the time-discounted squared geodesic angle between
+    states_*[2] ([N,T,3,3], losses.py:129-136).  On the MI355X both come from ONE launch and their gradients from another (`mf_pose_loss_*`,
+    `_FusedPoseLoss`) under the conditions of the position route plus: rotations on the device in X_pred's dtype with their inner 3x3
+    contiguous, an `R_gt` that does not require grad, rows of `R_pred` that do not alias.  One documented difference from autograd: where
+    `(tr - 1) / 2` is exactly +-1 (identical rotations, or an angle of exactly pi) torch's `arccos` backward yields 0 * inf = NaN / inf;
+    the kernel's rotation gradient is 0 there.  Outside the clip range both are 0.
     `monoforce_amd.losses._HIP_LOSS = False` keeps the ATen form everywhere."""
     X_gt, X_pred = states_gt[0], states_pred[0]
     # the cached drop-in step (api_cache.py): these ARE the states a replayed step handed out and this IS the call it was captured with ->
@@ -96,16 +103,37 @@ def physics_loss(states_pred, states_gt, pred_ts, gt_ts, gamma=0.9, rotation_los
         if nearest is None:
             nearest = nearest_steps_hip(pred_ts, gt_ts)
         return _FusedPhysicsLoss.apply(X_pred, X_gt, gt_ts, nearest, gamma)
+    if (_HIP_LOSS and rotation_loss and X_pred.is_cuda and X_pred.dtype in (torch.float32, torch.float64) and X_pred.dim() == 3
+            and X_pred.stride(2) == 1 and X_gt.is_cuda and gt_ts.is_cuda and (nearest is not None or pred_ts.is_cuda)
+            and X_gt.dtype == X_pred.dtype and gt_ts.dtype == X_pred.dtype and not X_gt.requires_grad and not gt_ts.requires_grad
+            and X_pred.numel() > 0 and X_gt.numel() > 0 and _rows_do_not_overlap(X_pred) and _rotations_take_the_hip_route(states_pred, states_gt)):
+        if nearest is None:
+            nearest = nearest_steps_hip(pred_ts, gt_ts)
+        return _FusedPoseLoss.apply(X_pred, states_pred[2], X_gt, states_gt[2], gt_ts, nearest, gamma)
     return physics_loss_aten(states_pred, states_gt, pred_ts, gt_ts, gamma=gamma, rotation_loss=rotation_loss, nearest=nearest)
 
 
-def _rows_do_not_overlap(X):
-    """True when no two (rollout, step) rows of X[B,T,3] share memory (an `expand`ed / stride-0 X_pred aliases rows: the scatter kernel's
-    plain stores would then drop contributions that the reference's index_put_ adds up)."""
+def _rows_do_not_overlap(X, width=3):
+    """True when no two (rollout, step) rows of X[B,T,...] (`width` contiguous scalars each: 3 for positions, 9 for rotations) share memory
+    (an `expand`ed / stride-0 X_pred aliases rows: the scatter kernel's plain stores would then drop contributions that the reference's
+    index_put_ adds up)."""
     (lo, nlo), (hi, nhi) = sorted([(abs(X.stride(0)), X.shape[0]), (abs(X.stride(1)), X.shape[1])])
-    if nlo > 1 and lo < 3:
+    if nlo > 1 and lo < width:
         return False
-    return not (nhi > 1 and hi < lo * (nlo - 1) + 3)
+    return not (nhi > 1 and hi < lo * (nlo - 1) + width)
+
+
+def _rotations_take_the_hip_route(states_pred, states_gt):
+    """The rotation half of `physics_loss`'s route decision: states_*[2] on the device, in the positions' dtype, [B,T,3,3] with the inner
+    3x3 contiguous, a ground truth that needs no gradient and predicted rows that do not alias."""
+    if len(states_pred) < 3 or len(states_gt) < 3:
+        return False
+    X_pred, X_gt, R_pred, R_gt = states_pred[0], states_gt[0], states_pred[2], states_gt[2]
+    for R, X in ((R_pred, X_pred), (R_gt, X_gt)):
+        if not (torch.is_tensor(R) and R.is_cuda and R.device == X_pred.device and R.dtype == X_pred.dtype and R.dim() == 4
+                and tuple(R.shape) == (*X.shape[:2], 3, 3) and R.stride(3) == 1 and R.stride(2) == 3):
+            return False
+    return not R_gt.requires_grad and _rows_do_not_overlap(R_pred, 9)
 
 
 def physics_loss_aten(states_pred, states_gt, pred_ts, gt_ts, gamma=0.9, rotation_loss=False, nearest=None):
@@ -122,6 +150,39 @@ def physics_loss_aten(states_pred, states_gt, pred_ts, gt_ts, gamma=0.9, rotatio
         return loss
     R_gt, R_sel = states_gt[2], states_pred[2][rows, nearest]
     return loss, (rotation_difference(R_sel, R_gt, reduction='none') * wt).mean()
+
+
+def translation_difference(x1, x2, reduction='mean'):
+    """Euclidean distance between positions [...,3]: its mean, its sum, or (any other `reduction`) the distances themselves (losses.py:36-45)."""
+    assert isinstance(x1, torch.Tensor) and isinstance(x2, torch.Tensor)
+    assert x1.shape == x2.shape
+    assert x1.shape[-1] == 3
+    dist = torch.norm(x1 - x2, dim=-1)
+    if reduction == 'mean':
+        return dist.mean()
+    if reduction == 'sum':
+        return dist.sum()
+    return dist
+
+
+def slerp(q1, q2, t_interval, diff_thresh=0.9995):
+    """Quaternion interpolation at the fractions `t_interval` [K] -> [K,4] (losses.py:14-34).  As the reference: above `diff_thresh` of the
+    dot product the quaternions are blended linearly and the whole [K,4] result is divided by ITS norm (one scalar, not one per row);
+    below, spherical interpolation with every row normalised; the shorter arc is not chosen (no sign flip for a negative dot product)."""
+    assert isinstance(q1, torch.Tensor) and isinstance(q2, torch.Tensor)
+    assert q1.shape == q2.shape == (4,)
+    assert isinstance(t_interval, torch.Tensor)
+    dot = (q1 * q2).sum()
+    if dot > diff_thresh:
+        q = (q1.unsqueeze(1) + t_interval * (q2 - q1).unsqueeze(1)).T
+        return q / torch.norm(q)
+    theta_0 = torch.acos(dot)
+    theta = theta_0 * t_interval
+    sin_t, sin_0 = torch.sin(theta), torch.sin(theta_0)
+    s0 = torch.cos(theta) - dot * sin_t / sin_0
+    s1 = sin_t / sin_0
+    q = s0.unsqueeze(1) * q1 + s1.unsqueeze(1) * q2
+    return q / torch.norm(q, dim=1, keepdim=True)
 
 
 def rotation_difference(R1, R2, reduction='mean'):
@@ -230,11 +291,105 @@ class _FusedPhysicsLoss(torch.autograd.Function):
         return gX, None, None, None, None
 
 
-def physics_loss_fused(states_pred, states_gt, pred_ts, gt_ts, gamma=0.9, nearest=None):
-    """`physics_loss` (position term) on the HIP kernels `mf_physics_loss_*`; same value and gradient."""
+class _FusedPoseLoss(torch.autograd.Function):
+    """`mf_pose_loss_value/bwd_*`: `physics_loss(..., rotation_loss=True)` as one gather-reduce kernel forward (both scalars) and one
+    scatter kernel backward; the gradients of `X_pred` and `R_pred` come back with the SAME strides as their inputs (the rollout's
+    time-major outputs: `mf_rollout_bwd_*` takes them as its gXs / gRs without a copy).  Where `(tr - 1) / 2` is exactly +-1 the rotation
+    gradient is 0 (torch's arccos backward: NaN / inf), see `physics_loss`."""
+
+    @staticmethod
+    def forward(ctx, X_pred, R_pred, X_gt, R_gt, gt_ts, nearest, gamma):
+        import ctypes as C
+        from . import _lib, _timing
+        _lib.require_hip_tensor(X_pred, 'X_pred')
+        _lib.require_hip_tensor(R_pred, 'R_pred')
+        _register_reset()
+        B, T1, _ = X_pred.shape
+        T2 = X_gt.shape[1]
+        dt = X_pred.dtype
+        assert X_pred.stride(2) == 1, 'positions must have their xyz components contiguous'
+        assert tuple(R_pred.shape) == (B, T1, 3, 3) and R_pred.dtype == dt and R_pred.stride(3) == 1 and R_pred.stride(2) == 3, \
+            'rotations must be [B,T1,3,3] in the dtype of the positions with their 3x3 contiguous'
+        assert tuple(R_gt.shape) == (B, T2, 3, 3), f'R_gt {tuple(R_gt.shape)} != {(B, T2, 3, 3)}'
+        sfx = {torch.float32: 'f32', torch.float64: 'f64'}[dt]
+        Xg = X_gt.to(dt).contiguous()
+        Rg = R_gt.to(dt).contiguous()
+        ts = gt_ts.to(dt).contiguous()
+        near = nearest if nearest.dtype == torch.int32 else nearest.to(torch.int32)
+        near = near.contiguous()
+        desc = _lib.MfPoseLossDesc(B=B, T1=T1, T2=T2, x_stride_b=X_pred.stride(0), x_stride_t=X_pred.stride(1),
+                                   r_stride_b=R_pred.stride(0), r_stride_t=R_pred.stride(1), gamma=float(gamma))
+        partial = torch.empty(2 * ((B * T2 + 255) // 256), dtype=dt, device=X_pred.device)
+        out = torch.empty(2, dtype=dt, device=X_pred.device)
+        cur = torch.cuda.current_stream(X_pred.device)
+        # when a backward will follow and the inputs are dense views (the rollout's outputs are), their gradient buffers are allocated now
+        # and cleared by the same launch
+
+        def grad_buffer(k, t):
+            if not ctx.needs_input_grad[k]:
+                return None
+            g = torch.empty_like(t)                        # preserve_format: the strides of the input
+            return g if g.stride() == t.stride() else None
+        gX, gR = grad_buffer(0, X_pred), grad_buffer(1, R_pred)
+        with torch.cuda.device(X_pred.device), _timing.timed('pose_loss_fwd', X_pred.device):
+            _lib.check(getattr(_lib.lib(), 'mf_pose_loss_value_' + sfx)(
+                C.byref(desc), _lib.ptr(X_pred), _lib.ptr(R_pred), _lib.ptr(Xg), _lib.ptr(Rg), _lib.ptr(ts), _lib.ptr(near), _lib.ptr(partial),
+                _lib.ptr(_ticket(X_pred.device, cur)), _lib.ptr(out), _lib.ptr(gX), C.c_longlong(0 if gX is None else gX.numel()),
+                _lib.ptr(gR), C.c_longlong(0 if gR is None else gR.numel()), C.c_void_p(cur.cuda_stream)), 'mf_pose_loss_value')
+        ctx.save_for_backward(X_pred, R_pred, Xg, Rg, ts, near)
+        ctx.gX, ctx.gR = gX, gR
+        ctx.set_materialize_grads(False)
+        ctx.desc, ctx.sfx = desc, sfx
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, gloss, grot):
+        import ctypes as C
+        from . import _lib, _timing
+        none = (None,) * 7
+        X_pred, R_pred, Xg, Rg, ts, near = ctx.saved_tensors
+        # a None upstream is a zero for that half: its gradient is not formed at all
+        want_x = gloss is not None and ctx.needs_input_grad[0]
+        want_r = grot is not None and ctx.needs_input_grad[1]
+        if not (want_x or want_r):
+            return none
+        (gX, gR), ctx.gX, ctx.gR = (ctx.gX, ctx.gR), None, None      # cleared by the forward launch; a second backward (retain_graph) refills
+
+        def zeroed(g, t):
+            if g is not None:
+                return g
+            g = torch.zeros_like(t)                       # preserve_format: same (dense) strides as the input
+            if g.stride() != t.stride():
+                g = torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device).zero_()
+            return g
+        gX = zeroed(gX, X_pred) if want_x else None
+        gR = zeroed(gR, R_pred) if want_r else None
+        zero = None
+        if gloss is None or grot is None:
+            zero = torch.zeros((), dtype=X_pred.dtype, device=X_pred.device)
+        gl = torch.stack([(zero if g is None else g.to(X_pred.dtype).reshape(())) for g in (gloss, grot)])
+        stream = C.c_void_p(torch.cuda.current_stream(X_pred.device).cuda_stream)
+        with torch.cuda.device(X_pred.device), _timing.timed('pose_loss_bwd', X_pred.device):
+            _lib.check(getattr(_lib.lib(), 'mf_pose_loss_bwd_' + ctx.sfx)(
+                C.byref(ctx.desc), _lib.ptr(X_pred), _lib.ptr(R_pred), _lib.ptr(Xg), _lib.ptr(Rg), _lib.ptr(ts), _lib.ptr(near), _lib.ptr(gl),
+                _lib.ptr(gX), _lib.ptr(gR), stream), 'mf_pose_loss_bwd')
+        return (gX, gR) + none[2:]
+
+
+def physics_loss_fused(states_pred, states_gt, pred_ts, gt_ts, gamma=0.9, nearest=None, rotation_loss=False):
+    """`physics_loss` on the HIP kernels: the position term on `mf_physics_loss_*`; with `rotation_loss=True` the pair
+    `(loss, loss_rot)` on `mf_pose_loss_*` (`_FusedPoseLoss`).  Same values and gradients, up to the rotation gradient's |cos| == 1
+    rule (`physics_loss`)."""
     if nearest is None:
         nearest = nearest_steps(pred_ts, gt_ts)
     X_pred = states_pred[0]
     if X_pred.dim() != 3 or X_pred.numel() == 0 or not _rows_do_not_overlap(X_pred):      # (aliased rows: the scatter kernel stores, the reference adds)
-        return physics_loss_aten(states_pred, states_gt, pred_ts, gt_ts, gamma=gamma, nearest=nearest.long())
-    return _FusedPhysicsLoss.apply(X_pred, states_gt[0], gt_ts, nearest, gamma)
+        return physics_loss_aten(states_pred, states_gt, pred_ts, gt_ts, gamma=gamma, rotation_loss=rotation_loss, nearest=nearest.long())
+    if not rotation_loss:
+        return _FusedPhysicsLoss.apply(X_pred, states_gt[0], gt_ts, nearest, gamma)
+    R_pred = states_pred[2]
+    if R_pred.stride(3) != 1 or R_pred.stride(2) != 3:
+        R_pred = R_pred.contiguous()
+    if not _rows_do_not_overlap(R_pred, 9):
+        return physics_loss_aten(states_pred, states_gt, pred_ts, gt_ts, gamma=gamma, rotation_loss=True, nearest=nearest.long())
+    return _FusedPoseLoss.apply(X_pred, R_pred.to(X_pred.dtype), states_gt[0], states_gt[2], gt_ts, nearest, gamma)

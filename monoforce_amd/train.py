@@ -203,6 +203,32 @@ class EncoderTrainStep:
         return self.losses(((imgs, rots, trans, intrins, post_rots, post_trans), hm_geom, hm_terrain, controls, pose0,
                             [Xs, Xds, Rs, Omegas], control_ts, traj_ts, self._nearest_for(control_ts, traj_ts)))
 
+    @torch.no_grad()
+    def evaluate(self, batch):
+        """One evaluation batch of `scripts/eval.py` (:93-104 `predict_states`, :146-153 the four numbers of its losses.csv) on the
+        reference's ROUGH sample tuple (the order of `compute_losses`): the two height-map losses, and `physics_loss(gamma=1.0,
+        rotation_loss=True)` of ONE rollout that starts from the first ground-truth state `(Xs[:,0], Xds[:,0], Rs[:,0], Omegas[:,0])`.
+        Returns a float32 device tensor `[4] = (H_g, H_t, XYZ, Rot)`; nothing is read back to the host, no parameter gradient is
+        touched, and the batch is left as it was (the rollout snaps its start position to the terrain in place: it gets a copy).
+        The maps go through the step's own `pool_k` staging -- the identity for k = 1, eval.py's case."""
+        from .losses import hm_loss
+        (imgs, rots, trans, intrins, post_rots, post_trans, hm_geom, hm_terrain, control_ts, controls, pose0,
+         traj_ts, Xs, Xds, Rs, Omegas) = batch
+        inputs = (imgs, rots, trans, intrins, post_rots, post_trans)
+        if self.fused_stage and imgs.is_cuda:
+            terrain = self.enc(*inputs, stage_k=self.pool_k)
+            z, mu = terrain['terrain_phys'], terrain['friction_phys']
+        else:
+            terrain = self.enc(*inputs)
+            z = self.terrain_preproc(terrain['terrain']).squeeze(1)
+            mu = self.terrain_preproc(terrain['friction']).squeeze(1)
+        l_geom = hm_loss(terrain['geom'][:, 0], hm_geom[:, 0], hm_geom[:, 1])                # eval.py:146
+        l_terr = hm_loss(terrain['terrain'][:, 0], hm_terrain[:, 0], hm_terrain[:, 1])       # eval.py:147
+        state0 = (Xs[:, 0].clone(), Xds[:, 0], Rs[:, 0].contiguous(), Omegas[:, 0])          # eval.py:98
+        states, _ = self.dp(z_grid=z, controls=controls, state=state0, friction=mu, _want_forces=False)
+        l_xyz, l_rot = physics_loss(states, [Xs, Xds, Rs, Omegas], control_ts, traj_ts, gamma=1.0, rotation_loss=True)     # eval.py:151-153
+        return torch.stack([l_geom.float(), l_terr.float(), l_xyz.float(), l_rot.float()])
+
     @staticmethod
     def _same_tensor(entry, *tensors):
         """True when `entry` was built from exactly these tensor OBJECTS at their current versions.  The entry holds the tensors, so
