@@ -13,6 +13,7 @@
 #pragma once
 #include "rollout_bwd_kernel.h"
 #include "rollout_cp_common.h"
+#include "stream_ring.h"
 #include <type_traits>
 
 namespace mf {
@@ -75,6 +76,9 @@ __global__ void __launch_bounds__(MODE == kCpStream ? 192 : (WIN ? 512 : 256)) M
 rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
   constexpr bool ODE = INTEG == MF_INTEG_ODEINT_EULER;
   constexpr bool LATE = MODE == kCpLate, STREAM = MODE == kCpStream, SAVED = MODE == kCpSaved || STREAM;
+  // HANDOFF (the float32 twelve-slot streaming kernels of the default integrator): the cell-gradient accumulator and its atomics live on the
+  // FETCHING waves -- the computing wave hands each step's two products back through the ring slot it read the step from (below)
+  constexpr bool HANDOFF = STREAM && SLOTS == 12 && sizeof(S) == 4 && ODE;
   using namespace cp;
   using M = Mth<S, std::is_same<S, float>::value>;      // float: fast math; double (the validation build): exact
   using Msk = typename MaskOf<S>::type;
@@ -679,10 +683,23 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
       constexpr int kSlots = SLOTS, kPlanesD = ODE ? 0 : 6, kPlanes = (XS_ONLY ? 10 : 12) + kPlanesD;      // dynamics(): six more (struct CoefD)
       constexpr bool kPow2 = (kSlots & (kSlots - 1)) == 0;
       __shared__ f4v ring[kSlots * kPlanes * 64];
-      __shared__ int flags[4];      // steps written, steps read; loss-value shares in l_part (fused loss value); the snap's cell in snap_c
+      __shared__ int flags[4];      // steps written, steps read (HANDOFF: steps answered); loss-value shares in l_part (fused loss value); the snap's cell in snap_c
       typedef __attribute__((address_space(3))) volatile int LdsCounter;      // (a generic volatile pointer would make FLAT accesses)
       LdsCounter* vflags = (LdsCounter*)flags;
       if (threadIdx.x == 0) { flags[0] = 0; flags[1] = 0; flags[2] = 0; flags[3] = 0; }
+      // HANDOFF: flags[1] counts the steps ANSWERED.  A step's answer -- its two cell-gradient products (nz, nm) -- is written by the computing
+      // wave over the first eight bytes of plane 0 of the slot the step was read from (R0, R1: in registers by then); the cell index stays in
+      // plane 7.  The fetching wave that owns the slot (stream_ring.h: ownership is fixed per wave) reads both back when it next writes the slot.
+      // The first kSlots steps have no predecessor in their slot: every slot starts as "cell 0, answer (0, 0)", which the accumulators (cell 0,
+      // sums 0) absorb without a flush -- no branch per step and no second copy of the pipeline for the first ring's worth.
+      constexpr unsigned kAnsPlane = 0u, kIdxPlane = 7u * 64u;
+      typedef S f2v __attribute__((ext_vector_type(2)));
+      if constexpr (HANDOFF) {
+        for (unsigned sl = threadIdx.x >> 6; sl < (unsigned)kSlots; sl += 3u) {
+          f4v* o = ring + sl * (unsigned)(kPlanes * 64) + lane;
+          o[kAnsPlane] = f4v{zero, zero, zero, zero}; o[kIdxPlane] = f4v{zero, zero, zero, idx_as(zero, 0)};
+        }
+      }
       __syncthreads();
       // MF_LOSS_VALUE_IN_BACKWARD: the loss VALUE as well.  The fetching waves add up the weighted squared errors of the stamped rows
       // they convert into dL/dXs anyway (the computing wave row 0's); at the end one partial sum per workgroup in a fixed order, and the
@@ -769,6 +786,7 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         // BATCH steps per batch (3; 2 where six waves share a CU's four SIMDs at 256 registers each: three register sets of three steps
         // spilled 200-250 bytes there, three sets of two do not)
         static_assert(kSlots % BATCH == 0 && (BATCH == 2 || BATCH == 3), "a batch must not wrap around the ring");
+        static_assert(!HANDOFF || stream_ring::fixed_ownership(kSlots, BATCH), "hand-off: a wave reads back the answers of the steps it wrote");
         struct Slot { StateIn st; Saved sv; UpIn up; S lg, lw; int sj; };      // stamp of the row, its weight and ground truth (fused loss)
         unsigned zero_lane = 0u;                                                   // 0, as a per-lane value the compiler cannot see through:
         asm("" : "+v"(zero_lane));                                                 // keeps the loads of the stamp tables VECTOR loads
@@ -802,9 +820,12 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         // form -- the ring carries the chain's COEFFICIENTS (struct Coef below), forty floats per lane and step.
         MF_PROF_T(t_fetcher);
         MF_PROF_ACC(acc_room); MF_PROF_ACC(acc_pub);
-        auto room = [&](int upto) {                 // until the steps with ordinals < upto may be written (their slots have been read)
+        // HANDOFF: "read" becomes "answered", which is up to one trip (two steps) later.  No deadlock: a computing wave blocked on ordinal p
+        // has answered >= p - 2 steps (it holds at most one unanswered step when it asks for two more), and room for ordinal p needs
+        // answered >= p + 1 - kSlots, so the wave that owes p can always write it (tools/stream_ring_model.cpp walks every interleaving).
+        auto room = [&](int upto) {                 // until the steps with ordinals < upto may be written (their slots have been read / answered)
           MF_PROF_T(t0);
-          while (upto - __builtin_amdgcn_readfirstlane(vflags[1]) > kSlots) __builtin_amdgcn_s_sleep(2);
+          while (!stream_ring::has_room(upto - 1, __builtin_amdgcn_readfirstlane(vflags[1]), kSlots)) __builtin_amdgcn_s_sleep(2);
           asm volatile("" ::: "memory");
           MF_PROF_SUM(acc_room, t0);
         };
@@ -831,9 +852,37 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         // (per step: everything is computed BEFORE the wave asks for room in the ring, the ten writes follow the grant, and the step is
         //  published at once when it is this wave's turn -- with whole batches behind one grant the computing wave idled 9 % of its time
         //  while a batch was rebuilt)
+        // HANDOFF: this wave's own cell accumulator over the answers of ITS steps -- today's accumulate-or-flush, one step at a time in
+        // ordinal order.  A lane's run on one cell is summed in two partial sums (one per fetching wave).  The atomics follow, in this wave's
+        // in-order memory queue, the loads of the batches in flight, which are waited for a whole batch later.
+        [[maybe_unused]] auto absorb = [&](unsigned ni, S nz, S nm) {
+          const bool same = !act | (ni == acc_idx);            // absent points contribute exact zeros: never flushed
+          if (!same) emit(acc_idx, acc_z, acc_m);
+          acc_idx = act ? ni : acc_idx;
+          acc_z = same ? acc_z + nz : nz;
+          acc_m = same ? acc_m + nm : nm;
+        };
+        [[maybe_unused]] auto absorb_slot = [&](unsigned slot) {       // the answer a slot holds (the caller has seen it counted in flags[1])
+          const f4v* in = ring + slot * (unsigned)(kPlanes * 64) + lane;
+          const f2v ans = *reinterpret_cast<const f2v*>(in + kAnsPlane);
+          const S ib = reinterpret_cast<const S*>(in + kIdxPlane)[3];
+          absorb((unsigned)idx_of(ib), ans.x, ans.y);
+        };
+        // The answer read back in one put() is absorbed in the NEXT one, right behind the point where that step's loads have arrived: the
+        // flush's atomics sit in the same in-order vmcnt queue as the rows, the record and the cells, and a wait for an OLDER load issued
+        // after a conditional atomic waits for the atomic too (the wait-count pass must assume it was not issued).  Behind the rebuild's
+        // wait the next such wait is a whole rebuild and a room() away.  (Absorbed where it was read -- in front of the next step's wait --
+        // the computing wave found the ring empty in 82 of 248 step pairs instead of 2: profiles/stream_scatter_ab.txt.)
+        [[maybe_unused]] unsigned pend_idx = 0u;      // "cell 0, answer (0, 0)": absorbed without a flush
+        [[maybe_unused]] S pend_z = zero, pend_m = zero;
         auto put = [&](const Slot& r, unsigned slot, int o) {
             Rec k;
             rebuild(r.st, r.sv, k);
+            if constexpr (HANDOFF) {
+              // (the empty asm ties the pending answer to this step's loaded values: the flush cannot be scheduled ahead of their wait)
+              asm("" : "+v"(pend_z), "+v"(pend_m) : "v"(k.zc), "v"(k.mcv), "v"(k.R2), "v"(k.cj), "v"(r.lg), "v"(r.up.gXs));
+              absorb(pend_idx, pend_z, pend_m);
+            }
             const S mw = inside(k.wraw, -a.omega_max, a.omega_max) ? one : zero;
             const S mG = inside(k.Gf, -mg, mg) ? one : zero;
             const S mF1 = inside(k.F1, -mg, mg) ? one : zero;
@@ -888,6 +937,13 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
             }
             room(o + 1);
             f4v* out = ring + slot * (unsigned)(kPlanes * 64) + lane;
+            [[maybe_unused]] f2v old_ans = {zero, zero};      // (HANDOFF only)
+            [[maybe_unused]] S old_idx = zero;
+            if constexpr (HANDOFF) {      // step o - kSlots (stream_ring::answer_in_slot), this wave's own: its cell and its answer, before they are overwritten
+              old_ans = *reinterpret_cast<const f2v*>(out + kAnsPlane);
+              old_idx = reinterpret_cast<const S*>(out + kIdxPlane)[3];
+              asm volatile("" ::: "memory");
+            }
             out[0] = p0; out[64] = p1; out[128] = p2; out[192] = p3; out[256] = p4; out[320] = p5; out[384] = p6; out[448] = p7; out[512] = p8; out[576] = p9;
             if constexpr (!XS_ONLY) {
               out[640] = f4v{first * r.up.gXds, first * r.up.gOm, r.up.gFs, r.up.gFf};
@@ -898,6 +954,7 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
               out[D0] = d0; out[D0 + 64] = d1; out[D0 + 128] = d2; out[D0 + 192] = d3; out[D0 + 256] = d4; out[D0 + 320] = d5;
             }
             publish_written(o + 1);
+            if constexpr (HANDOFF) { pend_idx = (unsigned)idx_of(old_idx); pend_z = old_ans.x; pend_m = old_ans.y; }
 #ifdef MF_STREAM_PROFILE
             if (o == 0) MF_PROF_ADD(18, t_k0);
 #endif
@@ -971,6 +1028,18 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         } else {
           snap_prepare();
         }
+        if constexpr (HANDOFF) {
+          // The answers still in this wave's slots: the steps nothing was written over, o >= n_steps - kSlots, in ordinal order; then what
+          // is left in the accumulator.  (Behind snap_prepare: the computing wave waits for flags[3] after its last step.)
+          MF_PROF_T(t_dr);
+          while (__builtin_amdgcn_readfirstlane(vflags[1]) != n_steps) __builtin_amdgcn_s_sleep(1);
+          asm volatile("" ::: "memory");
+          MF_PROF_ADD(25 + fk, t_dr);
+          absorb(pend_idx, pend_z, pend_m);      // (older than everything still in the slots)
+          for (int o = stream_ring::first_undrained(n_steps, kSlots); o < n_steps; ++o)
+            if (stream_ring::owner_of(o, BATCH) == fk) absorb_slot((unsigned)stream_ring::slot_of(o, kSlots));
+          if (act) emit(acc_idx, acc_z, acc_m);
+        }
         return;
       }
         // ---------------- the computing wave ----------------
@@ -997,6 +1066,7 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           S vp, inlr, wq, zc, mcv, wsb, wsa;      // -(1 / |u|) / res; d wq / d(fx, fy) / res
           S e, il, eci;                     // gate_col0 e / |col0|
           int idx;
+          unsigned off;                     // HANDOFF: the step's place in the ring (elements), where its answer goes
           // dynamics() only (struct "CoefD", six more planes): the adjoint-independent half of the Rodrigues step's backward
           S wn, kv, q0, q1, q2, Rk, kk, sn_, oc, cga, cgb, idn, idn2, ith;      // cga = h (1 - cos), cgb = h sin
           S M00, M01, M02, M10, M11, M12, M20, M21, M22;                      // M[m][j], every lane holds all nine
@@ -1022,7 +1092,8 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
 #endif
         };
         auto grab = [&](Coef& c, UpIn& up) {          // the next step out of the ring (it is there: ensure)
-          const f4v* o = ring + (kPow2 ? (unsigned)(consumed & (kSlots - 1)) : rslot) * (unsigned)(kPlanes * 64) + lane;
+          c.off = (kPow2 ? (unsigned)(consumed & (kSlots - 1)) : rslot) * (unsigned)(kPlanes * 64) + (unsigned)lane;
+          const f4v* o = ring + c.off;
           if constexpr (!kPow2) rslot = rslot + 1u == (unsigned)kSlots ? 0u : rslot + 1u;
           const f4v c0 = o[0], c1 = o[64], c2 = o[128], c3 = o[192], c4 = o[256], c5 = o[320], c6 = o[384], c7 = o[448], c8 = o[512], c9 = o[576];
           const S idx_bits = c7.w;       // (__builtin_bit_cast applied to the element expression itself reads element 0 of the vector)
@@ -1059,7 +1130,14 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           asm volatile("" ::: "memory");
           vflags[1] = consumed;                        // (LDS runs a wave's operations in order: the reads of grab are done by then)
         };
-        auto take = [&](Coef& c, UpIn& up) { ensure(1); grab(c, up); release(); };
+        auto take = [&](Coef& c, UpIn& up) {
+          ensure(1); grab(c, up);
+          if constexpr (HANDOFF) seen = vflags[0]; else release();
+        };
+        auto answered = [&](int k) {                  // HANDOFF: the first k steps' answers are in their slots (LDS runs a wave's operations in order)
+          asm volatile("" ::: "memory");
+          vflags[1] = k;
+        };
         // The chain of `vjp` (default integrator) on those coefficients.
         auto chain = [&](int n, const Coef& c, const UpIn& up) {
           const S h = c.h;
@@ -1142,7 +1220,9 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           const S ggp = dpp<0x51>(gg);                               // quad_perm [1,0,1,1]
           const S nz = mf_fma(gzq, c.wq, cgA * gg + cgB * ggp);
           const S nm = gmuq * c.wq;
-          {   // this lane's cell accumulator
+          if constexpr (HANDOFF) {      // back to the fetching wave that owns the slot: one 8-byte LDS store
+            *reinterpret_cast<f2v*>(ring + c.off + kAnsPlane) = f2v{nz, nm};
+          } else {   // this lane's cell accumulator
             const unsigned ni = (unsigned)c.idx;
             const bool same = !act | (ni == acc_idx);            // absent points contribute exact zeros: never flushed
             st_pending = !same;
@@ -1168,15 +1248,21 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         auto crunch = [&](int n, const Coef& c, const UpIn& up, Coef& c_next, UpIn& up_next, auto more, auto paired) {
           add_upstream_masked(up);
           if constexpr (decltype(paired)::value == 1) grab(c_next, up_next);                     // first of a pair: ensured by the loop
-          else if constexpr (decltype(paired)::value == 2) { grab(c_next, up_next); release(); } // second of a pair
-          else if constexpr (decltype(more)::value) take(c_next, up_next);
-          flush_stash();
+          else if constexpr (decltype(paired)::value == 2) {                                     // second of a pair
+            grab(c_next, up_next);
+            if constexpr (HANDOFF) seen = vflags[0]; else release();
+          } else if constexpr (decltype(more)::value) take(c_next, up_next);
+          if constexpr (!HANDOFF) flush_stash();
           if constexpr (GCTRL) bstore2(rGctrl, v_ctrl, gctrl_pending, gv_pending, gwc_pending);
 #ifdef MF_STREAM_NO_VJP      // A/B build (tools/build_variant.sh): the computing wave only takes the steps -- times the fetching wave alone
+                             // (HANDOFF: the steps are still counted as answered, and the fetching waves absorb the slots' stale coefficients as
+                             //  gradients -- wrong results, time only, as MF_STREAM_NO_ATOMIC)
           asm volatile("" :: "v"(c.R0), "v"(c.w1), "v"(c.f1), "v"(c.NnG), "v"(c.cmdv), "v"(c.csm), "v"(c.dcs), "v"(c.vp), "v"(c.zc), "v"(c.e));
 #else
           chain(n, c, up);
 #endif
+          // HANDOFF: a trip's two answers are counted at once (ordinal of step n: n_steps - 1 - n)
+          if constexpr (HANDOFF && decltype(paired)::value != 1) answered(n_steps - n);
         };
         using std::true_type;
         using std::false_type;
@@ -1298,9 +1384,9 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
   // the upstream gradient of output row 0 sits in the buffer the last iteration prefetched into
   MF_PROF_T(t_e0);
   UpIn up = (n_steps & 1) ? uB : uA;
-  flush_stash();
+  if constexpr (!HANDOFF) flush_stash();
   if constexpr (GCTRL) bstore2(rGctrl, v_ctrl, gctrl_pending, gv_pending, gwc_pending);
-  if (act) emit(acc_idx, acc_z, acc_m);      // what is still accumulated in registers
+  if constexpr (!HANDOFF) { if (act) emit(acc_idx, acc_z, acc_m); }      // what is still accumulated in registers (HANDOFF: the fetching waves')
   if constexpr (ODE) {                         // output 0 is the initial state itself (its forces are constant zeros)
     if (n_steps == 0) load_upstream(0, up);    // T == 1: the loop never ran
     add_upstream_state(up);

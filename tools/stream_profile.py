@@ -57,4 +57,6 @@ for B in [int(x) for x in os.environ.get('AB_B', '256,1024,2048').split(',')]:
     print(f'  compute tail {per[12] - per[20]:.0f}: waiting for the snap cell {per[7]:.0f} | flush + emit '
           f'{per[10]:.0f} | snap {per[11]:.0f} | rest {per[12] - per[20] - per[7] - per[10] - per[11]:.0f}', flush=True)
     print(f'  loss value finish on fetcher0 {per[21]:.0f} (max over workgroups {out[17]:.0f})', flush=True)
+    # (hand-off kernels: after its last step a fetching wave waits for the computing wave's last answer before it drains its slots)
+    print(f'  fetchers waiting for the last answer: fetcher0 {per[25]:.0f} fetcher1 {per[26]:.0f}', flush=True)
     print(f'  compute wave start -> end {per[12]:.0f} (max over workgroups {out[13]:.0f})  (ticks per launch and workgroup)', flush=True)
