@@ -1388,7 +1388,9 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
   if constexpr (GCTRL) bstore2(rGctrl, v_ctrl, gctrl_pending, gv_pending, gwc_pending);
   if constexpr (!HANDOFF) { if (act) emit(acc_idx, acc_z, acc_m); }      // what is still accumulated in registers (HANDOFF: the fetching waves')
   if constexpr (ODE) {                         // output 0 is the initial state itself (its forces are constant zeros)
-    if (n_steps == 0) load_upstream(0, up);    // T == 1: the loop never ran
+    // T == 1: the loop never ran.  (The streaming form holds row 0 already -- uZ, with the fused loss's dL/dXs formed from it: a reload
+    //  would hand the loss's raw Xs row on as the gradient.)
+    if constexpr (!STREAM) { if (n_steps == 0) load_upstream(0, up); }
     add_upstream_state(up);
   }
   lx = sum_points(lx); lxd = sum_points(lxd); lw = sum_points(lw);      // the adjoint of the initial state proper

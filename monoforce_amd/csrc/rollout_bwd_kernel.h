@@ -305,7 +305,9 @@ __device__ __forceinline__ void rollout_bwd_body(const RolloutBwdArgs<S>& a, S* 
     p.x = a.Xraw + in_row * 3; p.xd = a.Xds + in_row * 3; p.w = a.Om + in_row * 3; p.R = a.Rs + in_row * 9;
     p.c = ctrl + (size_t)m * 2; p.t = a.ts + m;
     p.g1 = a.gXs + out_row * a.sXs; p.g2 = a.gXds + out_row * a.sXds; p.g3 = a.gOm + out_row * a.sOm; p.g4 = a.gRs + out_row * a.sRs;
-    p.trow = INTEG == MF_INTEG_ODEINT_EULER ? min(m + 1, a.T - 1) : m;
+    // (the row's TIME INDEX is not clamped: at T = 1 the prologue's prefetch of "step 0" reads row 0 through the clamped pointers, and
+    //  counted as row 0 it used up the stamp of the start state's row before the epilogue's load of that row could meet it)
+    p.trow = INTEG == MF_INTEG_ODEINT_EULER ? m + 1 : m;
 #pragma unroll
     for (int j = 0; j < PPL; ++j) {
       const size_t pt = out_row * a.N + min(gl * PPL + j, a.N - 1);   // clamped: inactive slots read a valid row, masked at use

@@ -174,13 +174,14 @@ def time_grid(spec, n_controls, dtype):
     return ts[:min(n_full, n_controls)]
 
 
-def rollout(spec: RolloutSpec, z_grid, controls, state=None, friction=None, ts=None, joint_angles=None):
+def rollout(spec: RolloutSpec, z_grid, controls, state=None, friction=None, ts=None, joint_angles=None, snap=True):
     """`DPhysics.dphysics` (dphysics.py:530-594) for joint angles == 0.
 
     z_grid[B,H,W], controls[B,T,2], optional state=(x[B,3], xd[B,3], R[B,3,3], w[B,3]), friction[B,H,W].
     Like the reference it overwrites `state[0][:, 2]` in place with the terrain height under the robot.
     Returns ((Xs, Xds, Rs, Omegas), (F_springs, F_frictions)) laid out [B,T,...].
     `ts` overrides the time grid (the reference's linspace is built in the default dtype at construction).
+    `snap=False` (no reference equivalent; `MfRolloutDesc.skip_snap`) leaves the start height alone and continues from `state` as given.
     """
     dtype = z_grid.dtype
     B = z_grid.shape[0]
@@ -200,8 +201,9 @@ def rollout(spec: RolloutSpec, z_grid, controls, state=None, friction=None, ts=N
         x, xd, R, w = state
     if friction is None:                                                          # :562 (cfg.friction == ones)
         friction = torch.ones_like(z_grid)
-    p0 = P.repeat(B, 1, 1) @ R.transpose(1, 2) + x.unsqueeze(1)                   # :567-571
-    x[..., 2:3] = sample_grid(z_grid, p0[..., 0], p0[..., 1], spec.d_max, spec.grid_res).mean(1, keepdim=True)
+    if snap:
+        p0 = P.repeat(B, 1, 1) @ R.transpose(1, 2) + x.unsqueeze(1)               # :567-571
+        x[..., 2:3] = sample_grid(z_grid, p0[..., 0], p0[..., 1], spec.d_max, spec.grid_res).mean(1, keepdim=True)
 
     if ts is None:
         ts = time_grid(spec, controls.shape[1], dtype)
