@@ -101,7 +101,20 @@ __global__ void __launch_bounds__(256) reduce_grad_copies_kernel(S* __restrict__
   if (i >= n) return;
   S* p = pool + (long long)blockIdx.y * copies * n + i;
   S acc = (S)0;
-  for (int c = 0; c < copies; ++c) { acc += p[(long long)c * n]; p[(long long)c * n] = (S)0; }
+  // (the clearing zero goes only where something was scattered: most cells of most copies were never touched and are zero already --
+  //  a cell holding -0 compares equal and stays, which is as good a zero to add to; a NaN compares unequal and is cleared)
+  // Eight copies are loaded before the first of them is looked at: a store that depends on the value just read would otherwise put a
+  // whole memory round trip between one copy and the next.  The sum runs in copy order as before.
+  for (int c0 = 0; c0 < copies; c0 += 8) {
+    S v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = c0 + j < copies ? p[(long long)(c0 + j) * n] : (S)0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (c0 + j < copies) acc += v[j];
+      if (v[j] != (S)0) p[(long long)(c0 + j) * n] = (S)0;
+    }
+  }
   out[(long long)blockIdx.y * n + i] = acc;
 }
 

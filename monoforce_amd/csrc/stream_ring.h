@@ -30,5 +30,29 @@ constexpr int answer_in_slot(int o, int slots) { return o - slots; }
 // the first ordinal nothing is ever written over: the answers of [first_undrained, n_steps) are collected after the last write
 constexpr int first_undrained(int n_steps, int slots) { return n_steps > slots ? n_steps - slots : 0; }
 
+// ---- the answer ring ----
+// A variant of the hand-off that no kernel is built with at present: it was measured slower (the kernel change is
+// kept as tools/experiments/stream_answer_ring.patch, the protocol stays modelled in tools/stream_ring_model.cpp).
+// The answers do not travel through the coefficient slots there but through a ring of their own with `entries` places: the computing
+// wave stores the answer of ordinal o into entry entry_of(o), and the fetching wave that writes ordinal o reads the entry it is about to
+// reuse -- the answer of ordinal o - entries, its own step when fixed_ownership(entries, batch) -- in put(o), and what nothing was
+// written over (first_undrained(n_steps, entries) onwards) after its last step.  A coefficient slot is then free as soon as it has
+// been READ: the counter is "steps read" again (has_room with read in place of answered).
+constexpr int entry_of(int o, int entries) { return o % entries; }
+
+// the ordinal whose answer entry_of(o) holds when ordinal o is about to be written (negative: none, the entry's initial contents)
+constexpr int answer_in_entry(int o, int entries) { return o - entries; }
+
+// The computing wave counts `read = c` only after the chains of all ordinals <= c - kReadLead have stored their answers (a trip grabs
+// its two steps, counts them, and only then runs the second chain; the step grabbed last has not begun).
+constexpr int kReadLead = 3;
+
+// the last ordinal whose answer is certainly stored once room for ordinal o has been granted: the grant means read >= o + 1 - slots
+constexpr int last_answer_visible(int o, int slots) { return o + 1 - slots - kReadLead; }
+
+// true when the answer a fetching wave reads in put(o) is there by construction, so that the wave never waits for it: LDS runs one
+// wave's operations in order, and the computing wave's counter store follows its answer stores
+constexpr bool answer_visible_at_put(int entries, int slots) { return answer_in_entry(0, entries) <= last_answer_visible(0, slots); }
+
 }  // namespace stream_ring
 }  // namespace mf

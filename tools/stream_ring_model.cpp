@@ -1,8 +1,13 @@
 // Model of the streaming backward's ring protocol (monoforce_amd/csrc/rollout_bwd_cp_kernel.h, MODE = kCpStream): the computing wave and
 // the two fetching waves as state machines over the LDS counters -- published, answered, the snap flag -- and each wave's program
 // position, with the index arithmetic of csrc/stream_ring.h (the header the kernel uses).  Every interleaving of the three programs is
-// explored (breadth first over the reachable states) for n_steps = 1 .. 30 and every ring the kernels are built with:
+// explored (breadth first over the reachable states) for n_steps = 1 .. 30 (the answer ring: 1 .. 60, beyond two answer rings) and
+// every ring the kernels are built with:
 //   twelve slots, batches of three, hand-off   (the float32 default-integrator kernels: answers go back through the slots)
+//   twelve slots, batches of three, answer ring (not built: measured slower, DESIGN.md section 8 -- "answered" is "read" again, the
+//                                               answers go back through a ring of 24 entries of their own, written by the computing wave,
+//                                               consumed by the step's owner in put(o + 24) and in the final drain; the kernel side is
+//                                               tools/experiments/stream_answer_ring.patch)
 //   six slots, batches of three / of two       (the other streaming kernels: "answered" is "read", nothing goes back)
 //   six slots, batches of three, hand-off      (not built; ownership is fixed there too, so the protocol must hold)
 // It fails (exit status 1, one line per finding) on
@@ -10,8 +15,11 @@
 //   - a slot overwritten before its answer was consumed, or answered after it was overwritten,
 //   - an answer consumed twice, or never,
 //   - out-of-order publication (a counter that moves past a step not yet written, or backwards),
-//   - a blocked computing wave that has answered fewer than p - 2 steps (the invariant that rules out deadlock).
-// Exit status 0 and "explored <N> states" otherwise.  Host only:  c++ -std=c++17 -O2 -I monoforce_amd/csrc tools/stream_ring_model.cpp
+//   - a blocked computing wave that has answered fewer than p - 2 steps (the invariant that rules out deadlock),
+//   - answer ring: an entry read before its answer was written -- in put() that is a fetching wave that would have had to wait for an
+//     answer in steady state, which the kernel does not do --, an entry handed to a new step before its answer was consumed, an answer
+//     consumed twice, or never.
+// Exit status 0, "explored <N> states" (the total) and one "...: explored <n> states" line per configuration otherwise.  Host only:  c++ -std=c++17 -O2 -I monoforce_amd/csrc tools/stream_ring_model.cpp
 #include <cstdio>
 #include <cstdint>
 #include <cstring>
@@ -38,10 +46,15 @@ enum OpKind : int {
   C_ANSWER,     // hand-off: write the answer of ordinal arg into its slot
   C_COUNT,      // answered = arg
   C_SNAPWAIT,   // blocks until the snap's cell is ready
+  F_ATAKE,      // answer ring: read the entry ordinal arg will use (the answer of ordinal arg - entries), then leave arg's cell index there
+  F_ALLANS,     // answer ring: blocks until the computing wave has stored its last answer
+  F_ADRAIN,     // answer ring: read the answer of ordinal arg, still in its entry
+  C_AANSWER,    // answer ring: write the answer of ordinal arg into its entry
+  C_ALLANS,     // answer ring: all answers are stored
 };
 struct Op { int kind, arg; };
 
-struct Config { int n_steps, slots, batch; bool handoff; };
+struct Config { int n_steps, slots, batch; bool handoff; int entries; };      // entries > 0: the answer ring (then not `handoff`)
 
 // The programs, in the kernel's own order of operations.
 static std::vector<Op> fetcher_program(const Config& c, int fk) {
@@ -49,6 +62,7 @@ static std::vector<Op> fetcher_program(const Config& c, int fk) {
   auto put = [&](int o) {
     p.push_back({F_ROOM, o});
     if (c.handoff) p.push_back({F_TAKE, o});
+    if (c.entries) p.push_back({F_ATAKE, o});
     p.push_back({F_WRITE, o});
     p.push_back({F_PUBTRY, o + 1});
   };
@@ -66,6 +80,11 @@ static std::vector<Op> fetcher_program(const Config& c, int fk) {
     for (int o = sr::first_undrained(c.n_steps, c.slots); o < c.n_steps; ++o)
       if (sr::owner_of(o, c.batch) == fk) p.push_back({F_DRAIN, o});
   }
+  if (c.entries) {
+    p.push_back({F_ALLANS, 0});
+    for (int o = sr::first_undrained(c.n_steps, c.entries); o < c.n_steps; ++o)
+      if (sr::owner_of(o, c.batch) == fk) p.push_back({F_ADRAIN, o});
+  }
   return p;
 }
 static std::vector<Op> computer_program(const Config& c) {
@@ -74,6 +93,7 @@ static std::vector<Op> computer_program(const Config& c) {
   auto grab = [&]() { p.push_back({C_GRAB, consumed}); ++consumed; };
   auto finish = [&](int n) {      // the chain of step n is done (ordinal n_steps - 1 - n)
     if (c.handoff) p.push_back({C_ANSWER, c.n_steps - 1 - n});
+    if (c.entries) p.push_back({C_AANSWER, c.n_steps - 1 - n});
   };
   auto release = [&]() { if (!c.handoff) p.push_back({C_COUNT, consumed}); };      // the old form: counted when read
   int n = c.n_steps - 1;
@@ -91,17 +111,21 @@ static std::vector<Op> computer_program(const Config& c) {
   }
   finish(0);
   if (c.handoff) p.push_back({C_COUNT, c.n_steps});
+  if (c.entries) p.push_back({C_ALLANS, 0});
   p.push_back({C_SNAPWAIT, 0});
   return p;
 }
 
-constexpr int kMaxSlots = 12;
+constexpr int kMaxSlots = 12, kMaxEntries = 24;
 struct State {
   uint16_t pc[3];                 // fetching wave 0, fetching wave 1, computing wave
   int8_t published, answered, snap, consumed;
   int8_t pub[2];                  // a fetching wave's first written-but-unpublished ordinal
   int8_t ord[kMaxSlots];          // the ordinal a slot holds (-1: its initial contents)
   int8_t st[kMaxSlots];           // 0 written, 1 read by the computing wave, 2 answered, 3 answer consumed
+  int8_t allans;                  // answer ring: the computing wave's "all answered" flag
+  int8_t aord[kMaxEntries];       // answer ring: the ordinal an entry belongs to (-1: its initial contents)
+  int8_t ast[kMaxEntries];        // 0 handed to its step (cell index there), 2 answered, 3 answer consumed
 };
 static std::string key(const State& s) { return std::string(reinterpret_cast<const char*>(&s), sizeof(State)); }
 
@@ -109,7 +133,8 @@ struct Result { long states = 0; int findings = 0; };
 
 static void finding(Result& r, const Config& c, const char* what, int o) {
   if (r.findings < 20)
-    std::printf("FINDING n_steps %d slots %d batch %d %s: %s (ordinal %d)\n", c.n_steps, c.slots, c.batch, c.handoff ? "hand-off" : "read-counted", what, o);
+    std::printf("FINDING n_steps %d slots %d batch %d %s: %s (ordinal %d)\n", c.n_steps, c.slots, c.batch,
+                c.entries ? "answer ring" : (c.handoff ? "hand-off" : "read-counted"), what, o);
   ++r.findings;
 }
 
@@ -119,6 +144,7 @@ static Result explore(const Config& c) {
   State s0;
   std::memset(&s0, 0, sizeof(s0));
   for (int i = 0; i < kMaxSlots; ++i) { s0.ord[i] = -1; s0.st[i] = 3; }
+  for (int i = 0; i < kMaxEntries; ++i) { s0.aord[i] = -1; s0.ast[i] = 3; }
   std::unordered_set<std::string> seen;
   std::deque<State> todo;
   seen.insert(key(s0)); todo.push_back(s0);
@@ -194,6 +220,36 @@ static Result explore(const Config& c) {
           t.answered = (int8_t)op.arg;
           break;
         case C_SNAPWAIT: blocked = !s.snap; break;
+        case F_ATAKE: {
+          const int e = sr::entry_of(op.arg, c.entries), old = sr::answer_in_entry(op.arg, c.entries);
+          if (old >= 0) {
+            if (sr::owner_of(old, c.batch) != w) finding(res, c, "an answer read by the wave that did not write the step", old);
+            if (s.aord[e] != old) finding(res, c, "an answer entry holds an unexpected step", old);
+            else if (s.ast[e] < 2) finding(res, c, "a fetching wave would have had to wait for an answer: its entry read in put() before it was written", old);
+            else if (s.ast[e] == 3) finding(res, c, "an answer consumed twice", old);
+            if (old > sr::last_answer_visible(op.arg, c.slots)) finding(res, c, "an answer read in put() beyond stream_ring's visibility bound", old);
+          } else if (s.aord[e] != -1) finding(res, c, "initial contents expected in an answer entry", op.arg);
+          if (s.ast[e] < 3 && s.aord[e] >= 0 && s.aord[e] != old) finding(res, c, "an answer entry handed on before its answer was consumed", s.aord[e]);
+          t.aord[e] = (int8_t)op.arg; t.ast[e] = 0;
+          break;
+        }
+        case F_ALLANS: blocked = !s.allans; break;
+        case F_ADRAIN: {
+          const int e = sr::entry_of(op.arg, c.entries);
+          if (s.aord[e] != op.arg || s.ast[e] < 2) finding(res, c, "a drained answer entry read before it was written", op.arg);
+          else if (s.ast[e] == 3) finding(res, c, "an answer consumed twice", op.arg);
+          t.ast[e] = 3;
+          break;
+        }
+        case C_AANSWER: {
+          const int e = sr::entry_of(op.arg, c.entries);
+          if (s.aord[e] != op.arg) finding(res, c, "an answer written into an entry that was handed on (or never handed to its step)", op.arg);
+          else if (s.ast[e] != 0) finding(res, c, "an answer written twice", op.arg);
+          if (op.arg >= s.consumed) finding(res, c, "an answer written before the step was read", op.arg);
+          t.ast[e] = 2;
+          break;
+        }
+        case C_ALLANS: t.allans = 1; break;
       }
       if (blocked) continue;
       moved = true;
@@ -206,6 +262,9 @@ static Result explore(const Config& c) {
       if (c.handoff)
         for (int o = sr::first_undrained(c.n_steps, c.slots); o < c.n_steps; ++o)
           if (s.st[sr::slot_of(o, c.slots)] != 3) finding(res, c, "an answer never consumed", o);
+      if (c.entries)      // (the ordinals before first_undrained were consumed in put(): an entry is handed on only behind that check)
+        for (int o = sr::first_undrained(c.n_steps, c.entries); o < c.n_steps; ++o)
+          if (s.aord[sr::entry_of(o, c.entries)] != o || s.ast[sr::entry_of(o, c.entries)] != 3) finding(res, c, "an answer never consumed", o);
     }
     if (res.findings > 100) break;
   }
@@ -215,15 +274,22 @@ static Result explore(const Config& c) {
 int main() {
   static_assert(sr::fixed_ownership(12, 3) && sr::fixed_ownership(6, 3) && !sr::fixed_ownership(6, 2), "ring ownership");
   static_assert(sr::slot_of(13, 12) == 1 && sr::owner_of(5, 3) == 1 && sr::owner_of(6, 3) == 0 && sr::has_room(11, 0, 12) && !sr::has_room(12, 0, 12), "ring arithmetic");
-  const struct { int slots, batch; bool handoff; } rings[] = {{12, 3, true}, {6, 3, true}, {12, 3, false}, {6, 3, false}, {6, 2, false}};
-  long states = 0;
+  static_assert(sr::fixed_ownership(24, 3) && sr::entry_of(25, 24) == 1 && sr::answer_in_entry(30, 24) == 6 && sr::first_undrained(30, 24) == 6, "answer ring arithmetic");
+  static_assert(sr::answer_visible_at_put(24, 12) && sr::answer_visible_at_put(18, 12) && !sr::answer_visible_at_put(12, 12), "answer ring: visibility bound");
+  const struct { int slots, batch; bool handoff; int entries, horizons; const char* name; } rings[] = {
+      {12, 3, true, 0, 30, "12 slots, batches of 3, hand-off"},      {6, 3, true, 0, 30, "6 slots, batches of 3, hand-off"},
+      {12, 3, false, 0, 30, "12 slots, batches of 3, read-counted"}, {6, 3, false, 0, 30, "6 slots, batches of 3, read-counted"},
+      {6, 2, false, 0, 30, "6 slots, batches of 2, read-counted"},   {12, 3, false, 24, 60, "12 slots, batches of 3, read-counted, answer ring of 24"}};
+  constexpr int kRings = (int)(sizeof(rings) / sizeof(rings[0]));
+  long states = 0, per_ring[kRings] = {};
   int findings = 0;
-  for (const auto& r : rings)
-    for (int n = 1; n <= 30; ++n) {
-      const Result x = explore(Config{n, r.slots, r.batch, r.handoff});
-      states += x.states; findings += x.findings;
+  for (int k = 0; k < kRings; ++k)
+    for (int n = 1; n <= rings[k].horizons; ++n) {
+      const Result x = explore(Config{n, rings[k].slots, rings[k].batch, rings[k].handoff, rings[k].entries});
+      states += x.states; per_ring[k] += x.states; findings += x.findings;
     }
   if (findings) { std::printf("%d findings\n", findings); return 1; }
   std::printf("explored %ld states\n", states);
+  for (int k = 0; k < kRings; ++k) std::printf("%s, n_steps 1 .. %d: explored %ld states\n", rings[k].name, rings[k].horizons, per_ring[k]);
   return 0;
 }
