@@ -306,7 +306,9 @@ def _rollout_forward(ctx, opt, z, mu, controls, x_arg, xd0, R0, w0, joint_angles
             ctx.joint_angles = joint_angles.detach() if joint_angles is not None else None
             ctx.rec = f.rec
             # x0 now holds the snapped start position; a caller-visible buffer is copied, the module's own default is not
-            ctx.save_for_backward(controls, x0 if opt.x0_private else x0.clone(), xd0, R0, w0, opt.ts, f.Xraw, f.Xds, f.Rs, f.Om)
+            # (the maps too, as they came in: the backward reads them again through `ctx.maps` -- views or the tensors themselves -- and an
+            #  in-place edit between forward and backward must raise as it does for every other saved tensor, not meet the old states)
+            ctx.save_for_backward(controls, x0 if opt.x0_private else x0.clone(), xd0, R0, w0, opt.ts, f.Xraw, f.Xds, f.Rs, f.Om, z, mu)
     return outs
 
 

@@ -48,7 +48,7 @@ def to_input_shape(g, shape, expanded):
 def rollout_backward(ctx, ups, gloss=None):
     """Gradients of (z, mu, controls, x, xd0, R0, w0, joint_angles) -- the tensor arguments of `_RolloutFn.apply`, in its order -- from
     the six upstream gradients `ups`, or from `gloss` when the forward carried physics_loss itself."""
-    controls, x_init, xd0, R0, w0, ts, Xraw, Xds, Rs, Om = ctx.saved_tensors
+    controls, x_init, xd0, R0, w0, ts, Xraw, Xds, Rs, Om, _z_in, _mu_in = ctx.saved_tensors      # (the maps as given: saved for their version check)
     desc, mod = ctx.desc, ctx.mod
     z, mu, points = ctx.maps
     dev, dt = controls.device, controls.dtype
