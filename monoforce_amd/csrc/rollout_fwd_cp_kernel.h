@@ -99,7 +99,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
   // four different arrays in one store instruction, so this one takes per-lane 64-bit addresses
   S* v3base = p == 0 ? a.Xs : p == 1 ? a.Xds : p == 2 ? a.Om : (a.Xraw ? a.Xraw : a.Xs);
   const S sink_l = (p == 3 && a.Xraw) ? zero : a.sink;
-  const Msk m_xd = p == 1 ? ~(Msk)0 : (Msk)0, m_w = p == 2 ? ~(Msk)0 : (Msk)0, m_x = ~(m_xd | m_w);
+  const Msk m_xd = p == 1 ? ~(Msk)0 : (Msk)0, m_w = p == 2 ? ~(Msk)0 : (Msk)0;
   char* p3 = reinterpret_cast<char*>(v3base) + (size_t)(row0 * 3u + (unsigned)cc) * kS;
   const Rsrc rCtrl = make_rsrc(a.controls);
   unsigned o9 = (row0 * 9u + (unsigned)cc * 3u) * kS;
@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
   // the pending row from explicit values (the pipelined loop has already advanced x and R when it stores the row)
   auto emit_row = [&](S ex, S exd, S ew, S e0, S e1, S e2, unsigned adv) {
     const S vx = mf_fma(e2, sink_l, ex);          // Xs += Rs[..., :, 2] * m g / (k + 1e-6)   (dphysics.py:587-589)
-    const S v3 = mask_or(mask_or(mask_or(zero, vx, m_x), exd, m_xd), ew, m_w);
+    const S v3 = bfi(m_w, ew, bfi(m_xd, exd, vx));      // (two merges by quad role: the same bits as three masked values or-ed together)
     __builtin_nontemporal_store(v3, reinterpret_cast<S*>(p3));
     // (scalar base + RUNNING 32-bit per-lane offset: the step's advance is one vector add per array.  A scalar running pointer
     // costs s_add + s_addc, and scalar instructions take a full issue slot when a SIMD holds one wave: 22 of them per step were
@@ -239,13 +239,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     // n + 1 go out into the OTHER buffer set -- the loop below alternates two sets, so nothing is moved between iterations.
     S t_cur = a.T > 1 ? a.ts[1] : zero;
     const unsigned ctrl_step = (unsigned)a.ctrl_st * kS, v_ctrl_last = v_ctrl + (unsigned)(a.T - 1) * ctrl_step;
+    // the time stamps likewise: a running per-lane byte offset (every lane the same), clamped at the last stamp, and a VECTOR load that
+    // retires with the step's other loads -- the scalar index, address and load it replaces were five issue slots per step
+    unsigned v_ts = kS;                                          // stamp n + 1 (t_cur)
+    asm("" : "+v"(v_ts));                                        // (a per-lane value the compiler cannot see through)
+    const unsigned v_ts_last = (unsigned)max(a.T - 1, 0) * kS;
     auto ode_step = [&](int n, const Geo& g, Geo& g_next, S cv_n, S cw_n, S h, S& cv_next, S& cw_next, S& h_next) {
       // next step's controls and step size: loaded before the stores below (vmcnt retires in order)
       // (vector arithmetic on purpose -- a running per-lane offset clamped at the last row, the previous time stamp carried over:
       // the scalar index / address chains they replace were 10 scalar instructions per step, each a full issue slot here)
       v_ctrl = min(v_ctrl + ctrl_step, v_ctrl_last);
       bload2(rCtrl, v_ctrl, 0u, &cv_next, &cw_next);
-      const S t_next = a.ts[min(n + 2, a.T - 1)];
+      v_ts = min(v_ts + kS, v_ts_last);                        // stamp min(n + 2, T - 1)
+      const S t_next = *reinterpret_cast<const S*>(reinterpret_cast<const char*>(a.ts) + (size_t)v_ts);
       const Stamp stamp = loss_peek(n + 1);
       const S tv = cp_track(tv_v, tv_w, cv_n, cw_n);
       // ---- stream B: pose and geometry of step n + 1 (torchdiffeq fixed-grid euler: y_{n+1} = y_n + h f(t_n, y_n)) ----

@@ -1,8 +1,8 @@
 // Index arithmetic of the streaming backward's LDS ring (rollout_bwd_cp_kernel.h, MODE = kCpStream) in one host-compilable place:
 // plain constexpr functions, no HIP types.  The kernel uses them, and so does tools/stream_ring_model.cpp, which walks every
-// interleaving of the three waves over the ring's counters.
+// interleaving of the workgroup's waves over the ring's counters.
 //
-// Steps are numbered by ORDINAL in the order the computing wave takes them (ordinal 0 = the last time step).  The two fetching waves
+// Steps are numbered by ORDINAL in the order the computing wave takes them (ordinal 0 = the last time step).  The fetching waves (two or three)
 // write them in batches of `batch` consecutive ordinals, taking turns batch by batch; the ring has `slots` places, slots % batch == 0.
 // Counters: `published` = ordinals [0, published) are in the ring, advanced in order; `answered` = the computing wave is done with
 // ordinals [0, answered) -- it has read them and, in the hand-off form, written each one's answer (its two cell-gradient products)
@@ -18,7 +18,19 @@ constexpr int slot_of(int o, int slots) { return o % slots; }
 // the fetching wave (0 / 1) that writes ordinal o: batches alternate, the trailing partial batch included
 constexpr int owner_of(int o, int batch) { return (o / batch) & 1; }
 
-// true when a slot never changes hands: then the wave that writes ordinal o also wrote the ordinal it overwrites (hand-off needs it)
+// ... with `fetchers` fetching waves: wave k takes the batches k, k + fetchers, ...  (Three -- the twelve-slot hand-off kernels launched with
+// 256 threads -- are modelled and were built, tools/experiments/stream_three_fetchers.patch; measured slower)
+constexpr int owner_of(int o, int batch, int fetchers) { return (o / batch) % fetchers; }
+
+// the number of fetching waves of a workgroup of `threads` threads: every wave but the computing one
+constexpr int fetchers_of(int threads) { return threads / 64 - 1; }
+
+// whole batches wave k of `fetchers` writes out of n_full, and the wave that writes the trailing partial batch
+constexpr int batches_of(int n_full, int k, int fetchers) { return (n_full - k + fetchers - 1) / fetchers; }
+constexpr int tail_owner(int n_full, int fetchers) { return n_full % fetchers; }
+
+// true when a slot never changes hands: then the wave that writes ordinal o also wrote the ordinal it overwrites (the hand-off does NOT need it:
+// the wave about to overwrite a slot reads the answer in it, behind has_room -- whichever wave wrote the step)
 constexpr bool fixed_ownership(int slots, int batch) { return (slots / batch) % 2 == 0; }
 
 // the room condition: ordinal o may be written once the ordinal it overwrites, o - slots, has been answered

@@ -1,9 +1,12 @@
 // Model of the streaming backward's ring protocol (monoforce_amd/csrc/rollout_bwd_cp_kernel.h, MODE = kCpStream): the computing wave and
-// the two fetching waves as state machines over the LDS counters -- published, answered, the snap flag -- and each wave's program
-// position, with the index arithmetic of csrc/stream_ring.h (the header the kernel uses).  Every interleaving of the three programs is
+// the two (or three) fetching waves as state machines over the LDS counters -- published, answered, the snap flag -- and each wave's program
+// position, with the index arithmetic of csrc/stream_ring.h (the header the kernel uses).  Every interleaving of the programs is
 // explored (breadth first over the reachable states) for n_steps = 1 .. 30 (the answer ring: 1 .. 60, beyond two answer rings) and
 // every ring the kernels are built with:
 //   twelve slots, batches of three, hand-off   (the float32 default-integrator kernels: answers go back through the slots)
+//   ... the same with THREE fetching waves     (not built: measured slower, DESIGN.md section 8, tools/experiments/stream_three_fetchers.patch --
+//                                               those kernels launched with 256 threads: a slot changes hands -- ordinal o - 12 was written
+//                                               by wave (owner(o) + 2) mod 3 -- and the answer in it is read by whoever writes ordinal o)
 //   twelve slots, batches of three, answer ring (not built: measured slower, DESIGN.md section 8 -- "answered" is "read" again, the
 //                                               answers go back through a ring of 24 entries of their own, written by the computing wave,
 //                                               consumed by the step's owner in put(o + 24) and in the final drain; the kernel side is
@@ -11,7 +14,7 @@
 //   six slots, batches of three / of two       (the other streaming kernels: "answered" is "read", nothing goes back)
 //   six slots, batches of three, hand-off      (not built; ownership is fixed there too, so the protocol must hold)
 // It fails (exit status 1, one line per finding) on
-//   - a reachable state in which no wave can move before all three are done,
+//   - a reachable state in which no wave can move before all are done,
 //   - a slot overwritten before its answer was consumed, or answered after it was overwritten,
 //   - an answer consumed twice, or never,
 //   - out-of-order publication (a counter that moves past a step not yet written, or backwards),
@@ -19,6 +22,8 @@
 //   - answer ring: an entry read before its answer was written -- in put() that is a fetching wave that would have had to wait for an
 //     answer in steady state, which the kernel does not do --, an entry handed to a new step before its answer was consumed, an answer
 //     consumed twice, or never.
+// With an argument the protocol is MUTATED, to show that the model sees a broken one (tests/test_stream_three_fetchers_cpu.py):
+//   early-room   a fetching wave is granted room one slot early (has_room as if the ring had one slot more)
 // Exit status 0, "explored <N> states" (the total) and one "...: explored <n> states" line per configuration otherwise.  Host only:  c++ -std=c++17 -O2 -I monoforce_amd/csrc tools/stream_ring_model.cpp
 #include <cstdio>
 #include <cstdint>
@@ -54,7 +59,7 @@ enum OpKind : int {
 };
 struct Op { int kind, arg; };
 
-struct Config { int n_steps, slots, batch; bool handoff; int entries; };      // entries > 0: the answer ring (then not `handoff`)
+struct Config { int n_steps, slots, batch; bool handoff; int entries; int fetchers = 2; bool early_room = false; };      // entries > 0: the answer ring (then not `handoff`)
 
 // The programs, in the kernel's own order of operations.
 static std::vector<Op> fetcher_program(const Config& c, int fk) {
@@ -67,23 +72,24 @@ static std::vector<Op> fetcher_program(const Config& c, int fk) {
     p.push_back({F_PUBTRY, o + 1});
   };
   const int n_full = c.n_steps / c.batch;
-  for (int j = fk; j < n_full; j += 2) {
+  if (sr::batches_of(n_full, fk, c.fetchers) != (n_full > fk ? (n_full - fk + c.fetchers - 1) / c.fetchers : 0)) std::printf("FINDING batches_of(%d, %d, %d)\n", n_full, fk, c.fetchers);
+  for (int j = fk; j < n_full; j += c.fetchers) {
     p.push_back({F_BATCH, j * c.batch});
     for (int i = 0; i < c.batch; ++i) put(j * c.batch + i);
     p.push_back({F_PUBWAIT, (j + 1) * c.batch});
   }
-  if (fk == (n_full & 1))
+  if (fk == sr::tail_owner(n_full, c.fetchers))
     for (int o = n_full * c.batch; o < c.n_steps; ++o) { p.push_back({F_BATCH, o}); put(o); p.push_back({F_PUBWAIT, o + 1}); }
   if (fk == 1) p.push_back({F_SNAP, 0});
   if (c.handoff) {
     p.push_back({F_ALLDONE, 0});
     for (int o = sr::first_undrained(c.n_steps, c.slots); o < c.n_steps; ++o)
-      if (sr::owner_of(o, c.batch) == fk) p.push_back({F_DRAIN, o});
+      if (sr::owner_of(o, c.batch, c.fetchers) == fk) p.push_back({F_DRAIN, o});
   }
   if (c.entries) {
     p.push_back({F_ALLANS, 0});
     for (int o = sr::first_undrained(c.n_steps, c.entries); o < c.n_steps; ++o)
-      if (sr::owner_of(o, c.batch) == fk) p.push_back({F_ADRAIN, o});
+      if (sr::owner_of(o, c.batch, c.fetchers) == fk) p.push_back({F_ADRAIN, o});
   }
   return p;
 }
@@ -118,9 +124,9 @@ static std::vector<Op> computer_program(const Config& c) {
 
 constexpr int kMaxSlots = 12, kMaxEntries = 24;
 struct State {
-  uint16_t pc[3];                 // fetching wave 0, fetching wave 1, computing wave
+  uint16_t pc[4];                 // fetching waves 0 .. fetchers - 1, then the computing wave
   int8_t published, answered, snap, consumed;
-  int8_t pub[2];                  // a fetching wave's first written-but-unpublished ordinal
+  int8_t pub[3];                  // a fetching wave's first written-but-unpublished ordinal
   int8_t ord[kMaxSlots];          // the ordinal a slot holds (-1: its initial contents)
   int8_t st[kMaxSlots];           // 0 written, 1 read by the computing wave, 2 answered, 3 answer consumed
   int8_t allans;                  // answer ring: the computing wave's "all answered" flag
@@ -133,14 +139,17 @@ struct Result { long states = 0; int findings = 0; };
 
 static void finding(Result& r, const Config& c, const char* what, int o) {
   if (r.findings < 20)
-    std::printf("FINDING n_steps %d slots %d batch %d %s: %s (ordinal %d)\n", c.n_steps, c.slots, c.batch,
+    std::printf("FINDING n_steps %d slots %d batch %d fetchers %d %s: %s (ordinal %d)\n", c.n_steps, c.slots, c.batch, c.fetchers,
                 c.entries ? "answer ring" : (c.handoff ? "hand-off" : "read-counted"), what, o);
   ++r.findings;
 }
 
 static Result explore(const Config& c) {
   Result res;
-  const std::vector<Op> prog[3] = {fetcher_program(c, 0), fetcher_program(c, 1), computer_program(c)};
+  const int nw = c.fetchers + 1;
+  std::vector<Op> prog[4];
+  for (int k = 0; k < c.fetchers; ++k) prog[k] = fetcher_program(c, k);
+  prog[c.fetchers] = computer_program(c);
   State s0;
   std::memset(&s0, 0, sizeof(s0));
   for (int i = 0; i < kMaxSlots; ++i) { s0.ord[i] = -1; s0.st[i] = 3; }
@@ -152,7 +161,7 @@ static Result explore(const Config& c) {
     const State s = todo.front(); todo.pop_front();
     ++res.states;
     bool all_done = true, moved = false;
-    for (int w = 0; w < 3; ++w) {
+    for (int w = 0; w < nw; ++w) {
       if (s.pc[w] >= prog[w].size()) continue;
       all_done = false;
       const Op op = prog[w][s.pc[w]];
@@ -161,11 +170,13 @@ static Result explore(const Config& c) {
       const int sl = op.arg >= 0 ? sr::slot_of(op.arg, c.slots) : 0;
       switch (op.kind) {
         case F_BATCH: t.pub[w] = (int8_t)op.arg; break;
-        case F_ROOM: blocked = !sr::has_room(op.arg, s.answered, c.slots); break;
+        case F_ROOM: blocked = !sr::has_room(op.arg, s.answered, c.slots + (c.early_room ? 1 : 0)); break;
         case F_TAKE: {
           const int old = sr::answer_in_slot(op.arg, c.slots);
           if (old >= 0) {
-            if (sr::owner_of(old, c.batch) != w) finding(res, c, "an answer read by the wave that did not write the step", old);
+            // (two fetching waves on these rings: a slot stays with one wave; three: it does not, and need not -- stream_ring.h)
+            if (c.fetchers == 2 && sr::owner_of(old, c.batch) != w) finding(res, c, "an answer read by the wave that did not write the step", old);
+            if (c.fetchers == 3 && sr::owner_of(old, c.batch, 3) != (w + 2) % 3 && c.slots == 12 && c.batch == 3) finding(res, c, "an answer read by an unexpected wave", old);
             if (s.ord[sl] != old || s.st[sl] < 2) finding(res, c, "an answer read before it was written", old);
             else if (s.st[sl] == 3) finding(res, c, "an answer consumed twice", old);
             t.st[sl] = 3;
@@ -271,25 +282,33 @@ static Result explore(const Config& c) {
   return res;
 }
 
-int main() {
+int main(int argc, char** argv) {
+  const bool early_room = argc > 1 && std::strcmp(argv[1], "early-room") == 0;
+  if (argc > 1 && !early_room) { std::printf("usage: %s [early-room]\n", argv[0]); return 2; }
   static_assert(sr::fixed_ownership(12, 3) && sr::fixed_ownership(6, 3) && !sr::fixed_ownership(6, 2), "ring ownership");
+  static_assert(sr::owner_of(8, 3, 3) == 2 && sr::owner_of(9, 3, 3) == 0 && sr::owner_of(5, 3, 2) == sr::owner_of(5, 3) && sr::fetchers_of(256) == 3 && sr::fetchers_of(192) == 2 &&
+                sr::batches_of(7, 1, 3) == 2 && sr::batches_of(7, 0, 2) == 4 && sr::tail_owner(7, 3) == 1, "three fetching waves");
   static_assert(sr::slot_of(13, 12) == 1 && sr::owner_of(5, 3) == 1 && sr::owner_of(6, 3) == 0 && sr::has_room(11, 0, 12) && !sr::has_room(12, 0, 12), "ring arithmetic");
   static_assert(sr::fixed_ownership(24, 3) && sr::entry_of(25, 24) == 1 && sr::answer_in_entry(30, 24) == 6 && sr::first_undrained(30, 24) == 6, "answer ring arithmetic");
   static_assert(sr::answer_visible_at_put(24, 12) && sr::answer_visible_at_put(18, 12) && !sr::answer_visible_at_put(12, 12), "answer ring: visibility bound");
-  const struct { int slots, batch; bool handoff; int entries, horizons; const char* name; } rings[] = {
-      {12, 3, true, 0, 30, "12 slots, batches of 3, hand-off"},      {6, 3, true, 0, 30, "6 slots, batches of 3, hand-off"},
-      {12, 3, false, 0, 30, "12 slots, batches of 3, read-counted"}, {6, 3, false, 0, 30, "6 slots, batches of 3, read-counted"},
-      {6, 2, false, 0, 30, "6 slots, batches of 2, read-counted"},   {12, 3, false, 24, 60, "12 slots, batches of 3, read-counted, answer ring of 24"}};
+  const struct { int slots, batch; bool handoff; int entries, horizons; const char* name; int fetchers; } rings[] = {
+      {12, 3, true, 0, 30, "12 slots, batches of 3, hand-off", 2},      {6, 3, true, 0, 30, "6 slots, batches of 3, hand-off", 2},
+      {12, 3, false, 0, 30, "12 slots, batches of 3, read-counted", 2}, {6, 3, false, 0, 30, "6 slots, batches of 3, read-counted", 2},
+      {6, 2, false, 0, 30, "6 slots, batches of 2, read-counted", 2},   {12, 3, false, 24, 60, "12 slots, batches of 3, read-counted, answer ring of 24", 2},
+      {12, 3, true, 0, 30, "12 slots, batches of 3, hand-off, three fetching waves", 3}};
   constexpr int kRings = (int)(sizeof(rings) / sizeof(rings[0]));
   long states = 0, per_ring[kRings] = {};
   int findings = 0;
   for (int k = 0; k < kRings; ++k)
     for (int n = 1; n <= rings[k].horizons; ++n) {
-      const Result x = explore(Config{n, rings[k].slots, rings[k].batch, rings[k].handoff, rings[k].entries});
+      if (early_room && !rings[k].handoff) continue;      // (the mutation is shown on the hand-off rings)
+      const Result x = explore(Config{n, rings[k].slots, rings[k].batch, rings[k].handoff, rings[k].entries, rings[k].fetchers, early_room});
       states += x.states; per_ring[k] += x.states; findings += x.findings;
     }
   if (findings) { std::printf("%d findings\n", findings); return 1; }
   std::printf("explored %ld states\n", states);
-  for (int k = 0; k < kRings; ++k) std::printf("%s, n_steps 1 .. %d: explored %ld states\n", rings[k].name, rings[k].horizons, per_ring[k]);
+  // (the three-fetcher ring's line ends differently: the lines of the rings the kernels are built with keep their count)
+  for (int k = 0; k < kRings; ++k)
+    std::printf(rings[k].fetchers == 2 ? "%s, n_steps 1 .. %d: explored %ld states\n" : "%s, n_steps 1 .. %d: explored %ld states (four programs)\n", rings[k].name, rings[k].horizons, per_ring[k]);
   return 0;
 }
