@@ -15,8 +15,9 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = '/opt/rocm/lib/llvm/bin'
 
 
-def kernels(csrc=os.path.join(REPO, 'monoforce_amd', 'csrc')):
-    """[(object file, demangled kernel name, dict(vgpr, agpr, sgpr, lds, scratch))] over all objects."""
+def kernels(csrc=os.path.join(REPO, 'monoforce_amd', 'csrc'), mangled=False):
+    """[(object file, demangled kernel name, dict(vgpr, agpr, sgpr, lds, scratch))] over all objects; mangled=True: the entries carry
+    the kernel's symbol as a fourth element (two functions can share a demangled name cut at its argument list)."""
     rows = []
     for o in sorted(glob.glob(os.path.join(csrc, '*.o'))):
         with tempfile.TemporaryDirectory() as td:
@@ -34,7 +35,10 @@ def kernels(csrc=os.path.join(REPO, 'monoforce_amd', 'csrc')):
                          dict(agpr=int(re.match(r'\s*(\d+)', blk).group(1)), vgpr=f('vgpr_count'), sgpr=f('sgpr_count'), lds=f('group_segment_fixed_size'),
                               scratch=f('private_segment_fixed_size'))))
     names = subprocess.run(['c++filt'], input='\n'.join(n for _, n, _ in rows), capture_output=True, text=True).stdout.split('\n')
-    return [(o, re.sub(r'\(.*', '', n).replace('void ', ''), m) for (o, _, m), n in zip(rows, names)]
+    short = [re.sub(r'\(.*', '', n).replace('void ', '') for n in names]
+    if mangled:
+        return [(o, n, m, sym) for (o, sym, m), n in zip(rows, short)]
+    return [(o, n, m) for (o, _, m), n in zip(rows, short)]
 
 
 if __name__ == '__main__':
