@@ -2,10 +2,23 @@
 
 There is no CPU fallback: if the library has not been built (`python -c "import __graft_entry__ as g; g.build()"`
 or `make -C monoforce_amd/csrc`) every entry point raises.
+
+`launch` is the ONE way a kernel entry point is called: the tensors' device current, the optional `_timing` bracket, the dtype suffix,
+tensors -> pointers (`c_args`), the current stream last, `check` (one exception, `rollout_launch.GradPool.reduce`: the stream it was
+acquired on, not the current one).  `size_query` is the same for the two byte-count queries.  WHICH
+arguments an entry point takes is written down once, in the module that owns it: rollout_launch.py (`mf_rollout_*`,
+`mf_reduce_grad_copies_*`), splat.py (`mf_bev_*`), losses.py (`mf_physics_loss_*`, `mf_pose_loss_*`, `mf_nearest_steps_*`),
+terrain_stage.py, cloudproc.py, dphysics.py (`mf_interpolate_grid_*`), ops.py (MPPI and pose costs); tests/test_capi_cpu.py holds
+the tree to that.  Importing this module loads nothing: the library comes in at the first `lib()`.
 """
+import contextlib
 import ctypes as C
 import os
 import threading
+
+import torch
+
+from . import _timing
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'csrc', 'libmonoforce_hip.so')
@@ -111,9 +124,8 @@ def lib():
                     raise RuntimeError(
                         f'{LIB_PATH} is missing: build the HIP extension first (make -C monoforce_amd/csrc). '
                         'monoforce_amd has no CPU fallback.')
-                # torch bundles its own libamdhip64.so.7; import it FIRST so this library binds to the same HIP runtime
+                # torch bundles its own libamdhip64.so.7; it is imported FIRST (above) so this library binds to the same HIP runtime
                 # instance (loading /opt/rocm's copy first leaves the process with two runtimes and no device).
-                import torch  # noqa: F401
                 L = C.CDLL(os.environ.get('MONOFORCE_HIP_LIB', LIB_PATH))   # override: A/B builds of the kernels (tools/)
                 L.mf_last_error.restype = C.c_char_p
                 L.mf_version.restype = C.c_char_p
@@ -140,9 +152,45 @@ def check(rc, what):
         raise RuntimeError(f'{what} failed (code {rc}): {lib().mf_last_error().decode()}')
 
 
+def size_query(entry, desc):
+    """A byte-count query `entry(desc)` (not a launch: no device, no stream); the library answers a bad descriptor with 0 or -1 and
+    leaves the reason in mf_last_error."""
+    nbytes = int(getattr(lib(), entry)(C.byref(desc)))
+    if nbytes <= 0:
+        raise RuntimeError(f'{entry}: {lib().mf_last_error().decode()}')
+    return nbytes
+
+
 def ptr(t):
     """Device pointer of a torch tensor (None -> NULL)."""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def scalar_suffix(dtype):
+    if dtype == torch.float32:
+        return 'f32'
+    if dtype == torch.float64:
+        return 'f64'
+    raise TypeError(f'the HIP kernels compute in float32 or float64, got {dtype}')
+
+
+def stream_ptr(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def c_args(*args):
+    """Arguments as the C ABI takes them: a tensor -> its device pointer, a descriptor (`ctypes.Structure`) -> by reference; None (NULL),
+    ctypes scalars and arrays pass as they are."""
+    return [C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else C.byref(a) if isinstance(a, C.Structure) else a for a in args]
+
+
+def launch(entry, device, *args, dtype=None, timer=None):
+    """Call the kernel entry point `entry` (`dtype`: its `_f32` / `_f64` variant) on `device`'s current stream, with that device
+    CURRENT -- the library's policy reads the current device's CU count -- and, with `timer`, inside that `_timing`
+    bracket.  `args` go through `c_args`; the stream is appended.  A failure raises with the un-suffixed name."""
+    fn = getattr(lib(), entry if dtype is None else f'{entry}_{scalar_suffix(dtype)}')
+    with torch.cuda.device(device), (_timing.timed(timer, device) if timer else contextlib.nullcontext()):
+        check(fn(*c_args(*args), stream_ptr(device)), entry)
 
 
 def require_hip_tensor(t, name):

@@ -4,8 +4,6 @@ on the MI355X: per-cell maximum height of a point cloud plus the measurement mas
 axis = x).  The cloud may live on the host (it is copied to the GPU, the result comes back on the cloud's device) or on the
 GPU; there is no CPU implementation.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
@@ -45,8 +43,5 @@ def estimate_heightmap(points, grid_res, d_max, h_max, r_min=None, h_min=None):
                                 h_max=float(h_max), r_min=float(-1.0 if r_min is None else r_min), inv_res=float(1.0 / grid_res))
     scratch = torch.empty(n * n, dtype=torch.int32, device=dev)
     hm = torch.empty(2, n, n, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mf_estimate_heightmap_f32(C.byref(desc), _lib.ptr(pts), _lib.ptr(xb), _lib.ptr(xb), _lib.ptr(scratch),
-                                                        _lib.ptr(hm), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                   'mf_estimate_heightmap')
+    _lib.launch('mf_estimate_heightmap', dev, desc, pts, xb, xb, scratch, hm, dtype=torch.float32)
     return hm.to(home)

@@ -12,16 +12,14 @@ Outputs are `[B, T, ...]` *views* of time-major buffers -- exactly the layout th
 returns (`dphysics.py:515-526` permutes torchdiffeq's `[T, B, ...]` stacks); pass `contiguous_outputs=True` to the
 constructor to get batch-major contiguous tensors instead.
 """
-import ctypes as C
 import os
 from typing import NamedTuple, Optional
 
 import torch
 
-from . import _lib, _timing, rollout_launch as rl
+from . import _lib, losses, rollout_launch as rl
 from .dphys_config import DPhysConfig
 from .dphysics_bwd import rollout_backward
-from .rollout_launch import scalar_suffix as _scalar_suffix, stream_ptr as _stream_ptr
 
 __all__ = ['DPhysics', 'generate_controls', 'vw_to_track_vels', 'inertia_tensor', 'normalized', 'skew_symmetric']
 
@@ -90,10 +88,7 @@ def _default_state(controls, B, in_kernel=False):
         x, xd, R, w = buf[:3 * B].view(B, 3), buf[3 * B:6 * B].view(B, 3), buf[6 * B:15 * B].view(B, 3, 3), buf[15 * B:].view(B, 3)
         if in_kernel:
             return x, xd, R, w, True
-        fn = getattr(_lib.lib(), 'mf_rollout_default_state_' + _scalar_suffix(controls.dtype))
-        with torch.cuda.device(controls.device):
-            _lib.check(fn(C.c_int32(B), C.c_int32(controls.shape[1]), _lib.ptr(controls), _lib.ptr(x), _lib.ptr(xd), _lib.ptr(R), _lib.ptr(w),
-                          _stream_ptr(controls.device)), 'mf_rollout_default_state')
+        rl.default_state(controls, x, xd, R, w)
         return x, xd, R, w, False
     buf = torch.zeros(12 * B, dtype=controls.dtype, device=controls.device)
     x, R = buf[:3 * B].view(B, 3), buf[3 * B:].view(B, 3, 3)
@@ -160,7 +155,6 @@ class LossSpec:
         """The zero-initialised launch counter of the loss reductions, one per (device, stream) like `losses._ticket`: launches
         ordered on one stream share it (the kernel leaves it zero); two streams using one spec (a capture stream beside the default
         one) no longer tick the same counter."""
-        from . import losses
         losses._register_reset()
         t = losses._ticket(device, stream)
         self._tickets[(device.index, stream.cuda_stream)] = t      # a captured graph replays into this address: it lives as long as the spec
@@ -248,7 +242,7 @@ def _rollout_forward(ctx, opt, z, mu, controls, x_arg, xd0, R0, w0, joint_angles
             desc.has_joints = 1
             for i, v in enumerate(sum((list(p) for p in mod.dphys_cfg.joint_positions.values()), [])[:12]):
                 desc.joint_xyz[i] = float(v)
-        B, T, N = desc.B, desc.T, desc.N
+        B, N = desc.B, desc.N
         zmu_scratch, zmu_staged = _zmu_scratch(mod, desc, maps[0]), mod._staged_zmu(desc, z, mu)
         loss_val = lstruct = value_from = None
         if loss is not None:
@@ -277,13 +271,7 @@ def _rollout_forward(ctx, opt, z, mu, controls, x_arg, xd0, R0, w0, joint_angles
             # one wave per SIMD -- 0.165 -> 0.185 ms at B = 1024 -- where this launch is 0.012 ms.  The BACKWARD half of the fusion is
             # the one that pays: no loss-gradient launch, no [T][B][3] gradient rows (rollout_backward).
             near_b, gt_ts_b = spec.per_rollout(B)
-            Xp = outs[0]
-            ldesc = _lib.MfLossDesc(B=B, T1=T, T2=spec.T2, x_stride_b=Xp.stride(0), x_stride_t=Xp.stride(1), gamma=spec.gamma)
-            lpart = torch.empty((B * spec.T2 + 255) // 256, dtype=dt, device=dev)
-            with _timing.timed('physics_loss_fwd', dev):
-                _lib.check(getattr(_lib.lib(), 'mf_physics_loss_value_' + _scalar_suffix(dt))(
-                    C.byref(ldesc), _lib.ptr(Xp), _lib.ptr(X_gt), _lib.ptr(gt_ts_b), _lib.ptr(near_b), _lib.ptr(lpart), _lib.ptr(spec.ticket(dev, torch.cuda.current_stream(dev))),
-                    _lib.ptr(loss_val), None, C.c_longlong(0), _stream_ptr(dev)), 'mf_physics_loss_value')
+            losses.loss_value(outs[0], X_gt, gt_ts_b, near_b, spec.gamma, spec.ticket(dev, torch.cuda.current_stream(dev)), loss_val)
         if loss is not None:
             outs = (loss_val,) + outs
             # (the backward launch's scratch is allocated HERE: under a hipGraph capture the autograd thread must not allocate)
@@ -298,7 +286,7 @@ def _rollout_forward(ctx, opt, z, mu, controls, x_arg, xd0, R0, w0, joint_angles
             ctx.mod, ctx.desc, ctx.maps = mod, desc, maps
             # (the backward's record-reading kernel reads the shared maps interleaved too: the staged pair, or this scratch, which it fills itself)
             ctx.zmu = (zmu_scratch, zmu_staged) if maps[1] is not None else (None, None)
-            if ctx.zmu[1] is None and zmu_scratch is not None and dt == torch.float32 and _lib.lib().mf_rollout_fwd_stages_zmu(C.byref(desc)):
+            if ctx.zmu[1] is None and zmu_scratch is not None and dt == torch.float32 and rl.fwd_stages_zmu(desc):
                 ctx.zmu = (None, zmu_scratch)       # this launch filled the scratch: the backward reads it as it is
             ctx.z_shape, ctx.mu_shape = z.shape, (mu.shape if mu is not None else None)
             ctx.z_expanded = z.stride(0) == 0 and z.shape[0] > 1
@@ -476,7 +464,7 @@ class DPhysics(torch.nn.Module):
         z_grid = z_grid.to(dev)
         _lib.require_hip_tensor(z_grid, 'z_grid')
         dtype = z_grid.dtype
-        _scalar_suffix(dtype)        # float32 / float64 only: anything else is refused here, loudly
+        _lib.scalar_suffix(dtype)    # float32 / float64 only: anything else is refused here, loudly
         controls = controls.to(device=dev, dtype=dtype)
 
         own_state = state is None
@@ -574,7 +562,6 @@ class DPhysics(torch.nn.Module):
         from one small launch on its rows; 3 = the early-recompute component-parallel backward, 4097 .. 8192 rollouts, likewise; 0 in between
         -- 2049 .. 4096 rollouts, dynamics() 1025 .. 4096: the loss's own two launches are cheaper there; several stamps on one row: never)
         the same value and gradient come from the unfused route."""
-        from .losses import physics_loss_fused
         cp64 = z_grid.dtype == torch.float64 and self.points_per_lane == _lib.MF_LANES_COMPONENT      # the validation build of the fast kernels
         ok = (spec.fusable and not self.precise and (z_grid.dtype == torch.float32 or cp64) and spec.w.dtype == z_grid.dtype
               and not self.contiguous_outputs)
@@ -584,7 +571,7 @@ class DPhysics(torch.nn.Module):
         if ok:
             d = self._query_desc(B, spec.T, z_grid, force_stride=max(self.x_points.shape[1], 4), map_shared=1, layout=_lib.MF_LAYOUT_TIME_MAJOR)
             with torch.cuda.device(torch.device(self.device)):
-                fus = int(_lib.lib().mf_rollout_loss_fusable(C.byref(d)))
+                fus = rl.loss_fusable(d)
             # (saturated: the positions-only backward forms dL/dXs itself -- and the value, with `value_in_backward`; else the value comes
             #  from one small launch on the forward's rows)
             ok = fus == _lib.MF_LOSS_FUSE_BOTH or (fus in (_lib.MF_LOSS_FUSE_BACKWARD_SATURATED, _lib.MF_LOSS_FUSE_BACKWARD_EARLY)
@@ -597,7 +584,7 @@ class DPhysics(torch.nn.Module):
             states, forces = self.dphysics(z_grid, controls, state=state, friction=friction, _want_forces=want_forces)
             B_, T2 = X_gt.shape[:2]
             gt_ts = spec.gt_ts.unsqueeze(0).expand(B_, -1)
-            loss = physics_loss_fused(states, [X_gt], None, gt_ts, gamma=spec.gamma, nearest=spec.near.unsqueeze(0).expand(B_, -1))
+            loss = losses.physics_loss_fused(states, [X_gt], None, gt_ts, gamma=spec.gamma, nearest=spec.near.unsqueeze(0).expand(B_, -1))
             return (loss, states, forces) if want_forces else (loss, states)
         Xg = X_gt.detach().to(device=torch.device(self.device), dtype=z_grid.dtype).contiguous()
         assert Xg.shape == (B, spec.T2, 3), f'X_gt shape {tuple(Xg.shape)} != {(B, spec.T2, 3)}'
@@ -666,7 +653,7 @@ class DPhysics(torch.nn.Module):
         grid = torch.as_tensor(grid).to(dev)
         _lib.require_hip_tensor(grid, 'grid')
         dt = grid.dtype
-        sfx = _scalar_suffix(dt)
+        _lib.scalar_suffix(dt)       # float32 / float64 only, refused before anything else
         if any(torch.is_tensor(t) and t.requires_grad for t in (grid, x_query, y_query)) and torch.is_grad_enabled():
             raise RuntimeError('DPhysics.interpolate_grid: not differentiable on its own (gradients flow through forward())')
         B, H, W = grid.shape
@@ -681,10 +668,7 @@ class DPhysics(torch.nn.Module):
         n = torch.empty(B, N, 3, dtype=dt, device=dev) if return_normals else None
         cells = torch.empty(B, N, 4, dtype=torch.int32, device=dev) if return_cells else None
         frac = torch.empty(B, N, 2, dtype=dt, device=dev) if return_cells else None
-        with torch.cuda.device(dev):
-            _lib.check(getattr(_lib.lib(), 'mf_interpolate_grid_' + sfx)(C.byref(desc), _lib.ptr(gc), _lib.ptr(xq), _lib.ptr(yq), _lib.ptr(z),
-                                                                         _lib.ptr(n), _lib.ptr(cells), _lib.ptr(frac), _stream_ptr(dev)),
-                       'mf_interpolate_grid')
+        _lib.launch('mf_interpolate_grid', dev, desc, gc, xq, yq, z, n, cells, frac, dtype=dt)
         out = (z,) + ((n,) if return_normals else ()) + ((cells, frac) if return_cells else ())
         return out[0] if len(out) == 1 else out
 

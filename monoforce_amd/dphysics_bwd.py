@@ -4,7 +4,6 @@
 Replaces the T x ~300-node autograd graph of the reference (`loss.backward()` through
 `/root/reference/monoforce/src/monoforce/models/traj_predictor/dphysics.py:172-272,467-528`) with one kernel launch.
 """
-import ctypes as C
 import os
 
 import torch
@@ -61,11 +60,11 @@ def rollout_backward(ctx, ups, gloss=None):
             # ... unless the launch sends its cell gradients through per-workgroup LDS windows (mf_rollout_bwd_window: saturated positions-only
             # launches): a workgroup adds its window to ONE copy once, at its end -- 256 copies cost a 0.125 ms reduction for 0.035 ms of kernel time
             if (WIN_GRAD_COPIES and dt == torch.float32 and (gloss is not None or ups[0] is not None) and all(u is None for u in ups[1:])
-                    and _lib.lib().mf_rollout_bwd_window(C.byref(desc))):
+                    and rl.bwd_window(desc)):
                 copies = min(copies, WIN_GRAD_COPIES)
             desc.grad_copies = copies
         # the control gradient is skipped where nobody wants it and the chosen kernels can leave it out (mf_rollout_bwd_wants_gcontrols)
-        need_gc = need_controls or bool(_lib.lib().mf_rollout_bwd_wants_gcontrols(C.byref(desc)))      # (round 6: never forced by the library)
+        need_gc = need_controls or rl.bwd_wants_gcontrols(desc)      # (round 6: never forced by the library)
         lstruct = None
         if gloss is not None:       # the forward carried physics_loss itself (MfRolloutLoss): the kernel forms dL/dXs from Xs and the ground truth
             spec, X_gt, Xs_rows, loss_out = ctx.loss

@@ -1,8 +1,17 @@
 """Losses that sit directly on top of the rollout / encoder outputs (plain torch; they run on whatever device the
 tensors are on).  Semantics of `/root/reference/monoforce/src/monoforce/losses.py`: `physics_loss` :102-138, `hm_loss`
 :77-99, `total_variation` :68-74, `rotation_difference` :48-65, `translation_difference` :36-45, `slerp` :14-34.
+
+The loss kernels of the C ABI (`mf_physics_loss_*`, `mf_pose_loss_*`, `mf_nearest_steps_*`) are marshalled here and nowhere else: one
+function per entry point (`loss_value`, `loss_backward`, `pose_loss_value`, `pose_loss_backward`, `nearest_steps_hip`) builds the
+descriptor, sizes the partial sums and launches through `_lib.launch`; the autograd functions below and the rollout's fused-loss route
+(dphysics.py) call them.
 """
+import ctypes as C
+
 import torch
+
+from . import _lib
 
 _HIP_LOSS = True      # physics_loss on GPU tensors runs on the mf_physics_loss_* kernels (False: the reference's ATen form)
 
@@ -44,8 +53,6 @@ def nearest_steps_hip(pred_ts, gt_ts):
     indices.  Same indices (the first minimum, like torch.argmin); int32 [N,T2].  Expanded (stride-0) stamp rows are read as they are.
     One documented difference: a NaN among the differences is SKIPPED here (index 0 only when every difference is NaN), where
     torch.argmin returns the first NaN's index -- stamps are finite in every caller of the reference."""
-    import ctypes as C
-    from . import _lib
     _lib.require_hip_tensor(pred_ts, 'pred_ts')
     dt = torch.promote_types(pred_ts.dtype, gt_ts.dtype)
     if dt not in (torch.float32, torch.float64):
@@ -59,10 +66,8 @@ def nearest_steps_hip(pred_ts, gt_ts):
         return t if t.stride(1) == 1 or t.shape[1] == 1 else t.contiguous()
     p, g = rows(pred_ts), rows(gt_ts)
     out = torch.empty(N, T2, dtype=torch.int32, device=pred_ts.device)
-    fn = getattr(_lib.lib(), 'mf_nearest_steps_' + ('f32' if dt == torch.float32 else 'f64'))
-    with torch.cuda.device(pred_ts.device):
-        _lib.check(fn(C.c_int32(N), C.c_int32(T1), C.c_int32(T2), _lib.ptr(p), C.c_longlong(p.stride(0)), _lib.ptr(g), C.c_longlong(g.stride(0)),
-                      _lib.ptr(out), C.c_void_p(torch.cuda.current_stream(pred_ts.device).cuda_stream)), 'mf_nearest_steps')
+    _lib.launch('mf_nearest_steps', pred_ts.device, C.c_int32(N), C.c_int32(T1), C.c_int32(T2), p, C.c_longlong(p.stride(0)), g,
+                C.c_longlong(g.stride(0)), out, dtype=dt)
     return out
 
 
@@ -223,34 +228,63 @@ def _reset_tickets():
 
 
 def _register_reset():
-    from . import _lib
     if _reset_tickets not in _lib.ON_ERROR:
         _lib.ON_ERROR.append(_reset_tickets)
 
 
+def _numel(g):
+    return C.c_longlong(0 if g is None else g.numel())
+
+
+def loss_value(X_pred, X_gt, gt_ts, near, gamma, ticket, loss, gX=None):
+    """One `mf_physics_loss_value_*` launch: `loss` (a scalar tensor) <- physics_loss of X_pred [B,T1,3] (any strides with xyz dense) against
+    X_gt [B,T2,3], gt_ts [B,T2] and near [B,T2] int32, all contiguous in X_pred's dtype; `ticket`: `_ticket`'s counter of the current
+    stream; `gX`: a gradient buffer with X_pred's strides that the same launch clears.  Returns the descriptor, which the backward takes."""
+    (B, T1, _), T2 = X_pred.shape, X_gt.shape[1]
+    desc = _lib.MfLossDesc(B=B, T1=T1, T2=T2, x_stride_b=X_pred.stride(0), x_stride_t=X_pred.stride(1), gamma=float(gamma))
+    partial = torch.empty((B * T2 + 255) // 256, dtype=X_pred.dtype, device=X_pred.device)
+    _lib.launch('mf_physics_loss_value', X_pred.device, desc, X_pred, X_gt, gt_ts, near, partial, ticket, loss, gX, _numel(gX),
+                dtype=X_pred.dtype, timer='physics_loss_fwd')
+    return desc
+
+
+def loss_backward(desc, X_pred, X_gt, gt_ts, near, gloss, gX):
+    """One `mf_physics_loss_bwd_*` launch: the rows of the zeroed `gX` that `near` names <- gloss [1] x d loss / d X_pred."""
+    _lib.launch('mf_physics_loss_bwd', X_pred.device, desc, X_pred, X_gt, gt_ts, near, gloss, gX, dtype=X_pred.dtype, timer='physics_loss_bwd')
+
+
+def pose_loss_value(X_pred, R_pred, X_gt, R_gt, gt_ts, near, gamma, ticket, out, gX=None, gR=None):
+    """One `mf_pose_loss_value_*` launch: out [2] <- (loss, loss_rot); arguments as `loss_value` plus the rotations [B,T,3,3] (inner 3x3
+    dense) and their gradient buffer.  Returns the descriptor."""
+    (B, T1, _), T2 = X_pred.shape, X_gt.shape[1]
+    desc = _lib.MfPoseLossDesc(B=B, T1=T1, T2=T2, x_stride_b=X_pred.stride(0), x_stride_t=X_pred.stride(1),
+                               r_stride_b=R_pred.stride(0), r_stride_t=R_pred.stride(1), gamma=float(gamma))
+    partial = torch.empty(2 * ((B * T2 + 255) // 256), dtype=X_pred.dtype, device=X_pred.device)
+    _lib.launch('mf_pose_loss_value', X_pred.device, desc, X_pred, R_pred, X_gt, R_gt, gt_ts, near, partial, ticket, out, gX, _numel(gX),
+                gR, _numel(gR), dtype=X_pred.dtype, timer='pose_loss_fwd')
+    return desc
+
+
+def pose_loss_backward(desc, X_pred, R_pred, X_gt, R_gt, gt_ts, near, gl, gX, gR):
+    """One `mf_pose_loss_bwd_*` launch: gl [2] = the two upstream gradients; `gX` / `gR` zeroed, None = that half is not formed."""
+    _lib.launch('mf_pose_loss_bwd', X_pred.device, desc, X_pred, R_pred, X_gt, R_gt, gt_ts, near, gl, gX, gR, dtype=X_pred.dtype,
+                timer='pose_loss_bwd')
+
+
 class _FusedPhysicsLoss(torch.autograd.Function):
-    """`mf_physics_loss_fwd/bwd_*`: one gather-reduce kernel forward, one scatter kernel backward; the gradient comes back
+    """`mf_physics_loss_value/bwd_*`: one gather-reduce kernel forward, one scatter kernel backward; the gradient comes back
     with the SAME strides as `X_pred` (for the rollout's time-major outputs: ready for `mf_rollout_bwd_*` without a copy)."""
 
     @staticmethod
     def forward(ctx, X_pred, X_gt, gt_ts, nearest, gamma):
-        import ctypes as C
-        from . import _lib, _timing
         _lib.require_hip_tensor(X_pred, 'X_pred')
         _register_reset()
-        B, T1, _ = X_pred.shape
-        T2 = X_gt.shape[1]
         assert X_pred.stride(2) == 1, 'positions must have their xyz components contiguous'
-        sfx = {torch.float32: 'f32', torch.float64: 'f64'}[X_pred.dtype]
         Xg = X_gt.to(X_pred.dtype).contiguous()
         ts = gt_ts.to(X_pred.dtype).contiguous()
         near = nearest if nearest.dtype == torch.int32 else nearest.to(torch.int32)
         near = near.contiguous()
-        desc = _lib.MfLossDesc(B=B, T1=T1, T2=T2, x_stride_b=X_pred.stride(0), x_stride_t=X_pred.stride(1), gamma=float(gamma))
-        partial = torch.empty((B * T2 + 255) // 256, dtype=X_pred.dtype, device=X_pred.device)
         loss = torch.empty((), dtype=X_pred.dtype, device=X_pred.device)
-        cur = torch.cuda.current_stream(X_pred.device)
-        stream = C.c_void_p(cur.cuda_stream)
         # the mean is finished inside the launch (no `partial.sum() * c`: two launches fewer forward, two fewer backward)
         # when a backward will follow and X_pred is a dense view (the rollout's outputs are), its gradient buffer is allocated now
         # and cleared by the same launch
@@ -259,21 +293,14 @@ class _FusedPhysicsLoss(torch.autograd.Function):
             gX = torch.empty_like(X_pred)                  # preserve_format: the strides of X_pred
             if gX.stride() != X_pred.stride():
                 gX = None
-        with torch.cuda.device(X_pred.device), _timing.timed('physics_loss_fwd', X_pred.device):
-            _lib.check(getattr(_lib.lib(), 'mf_physics_loss_value_' + sfx)(C.byref(desc), _lib.ptr(X_pred), _lib.ptr(Xg), _lib.ptr(ts),
-                                                                           _lib.ptr(near), _lib.ptr(partial), _lib.ptr(_ticket(X_pred.device, cur)),
-                                                                           _lib.ptr(loss), _lib.ptr(gX), C.c_longlong(0 if gX is None else gX.numel()),
-                                                                           stream), 'mf_physics_loss_value')
+        ctx.desc = loss_value(X_pred, Xg, ts, near, gamma, _ticket(X_pred.device, torch.cuda.current_stream(X_pred.device)), loss, gX)
         ctx.save_for_backward(X_pred, Xg, ts, near)
         ctx.gX = gX
         ctx.set_materialize_grads(False)
-        ctx.desc, ctx.sfx = desc, sfx
         return loss
 
     @staticmethod
     def backward(ctx, gloss):
-        import ctypes as C
-        from . import _lib, _timing
         if gloss is None:
             return None, None, None, None, None
         X_pred, Xg, ts, near = ctx.saved_tensors
@@ -283,11 +310,7 @@ class _FusedPhysicsLoss(torch.autograd.Function):
             if gX.stride() != X_pred.stride():
                 gX = torch.empty_strided(X_pred.shape, X_pred.stride(), dtype=X_pred.dtype, device=X_pred.device).zero_()
         gl = gloss.to(X_pred.dtype).reshape(1).contiguous()
-        stream = C.c_void_p(torch.cuda.current_stream(X_pred.device).cuda_stream)
-        with torch.cuda.device(X_pred.device), _timing.timed('physics_loss_bwd', X_pred.device):
-            _lib.check(getattr(_lib.lib(), 'mf_physics_loss_bwd_' + ctx.sfx)(C.byref(ctx.desc), _lib.ptr(X_pred), _lib.ptr(Xg), _lib.ptr(ts),
-                                                                             _lib.ptr(near), _lib.ptr(gl), _lib.ptr(gX), stream),
-                       'mf_physics_loss_bwd')
+        loss_backward(ctx.desc, X_pred, Xg, ts, near, gl, gX)
         return gX, None, None, None, None
 
 
@@ -299,8 +322,6 @@ class _FusedPoseLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X_pred, R_pred, X_gt, R_gt, gt_ts, nearest, gamma):
-        import ctypes as C
-        from . import _lib, _timing
         _lib.require_hip_tensor(X_pred, 'X_pred')
         _lib.require_hip_tensor(R_pred, 'R_pred')
         _register_reset()
@@ -311,17 +332,12 @@ class _FusedPoseLoss(torch.autograd.Function):
         assert tuple(R_pred.shape) == (B, T1, 3, 3) and R_pred.dtype == dt and R_pred.stride(3) == 1 and R_pred.stride(2) == 3, \
             'rotations must be [B,T1,3,3] in the dtype of the positions with their 3x3 contiguous'
         assert tuple(R_gt.shape) == (B, T2, 3, 3), f'R_gt {tuple(R_gt.shape)} != {(B, T2, 3, 3)}'
-        sfx = {torch.float32: 'f32', torch.float64: 'f64'}[dt]
         Xg = X_gt.to(dt).contiguous()
         Rg = R_gt.to(dt).contiguous()
         ts = gt_ts.to(dt).contiguous()
         near = nearest if nearest.dtype == torch.int32 else nearest.to(torch.int32)
         near = near.contiguous()
-        desc = _lib.MfPoseLossDesc(B=B, T1=T1, T2=T2, x_stride_b=X_pred.stride(0), x_stride_t=X_pred.stride(1),
-                                   r_stride_b=R_pred.stride(0), r_stride_t=R_pred.stride(1), gamma=float(gamma))
-        partial = torch.empty(2 * ((B * T2 + 255) // 256), dtype=dt, device=X_pred.device)
         out = torch.empty(2, dtype=dt, device=X_pred.device)
-        cur = torch.cuda.current_stream(X_pred.device)
         # when a backward will follow and the inputs are dense views (the rollout's outputs are), their gradient buffers are allocated now
         # and cleared by the same launch
 
@@ -331,21 +347,15 @@ class _FusedPoseLoss(torch.autograd.Function):
             g = torch.empty_like(t)                        # preserve_format: the strides of the input
             return g if g.stride() == t.stride() else None
         gX, gR = grad_buffer(0, X_pred), grad_buffer(1, R_pred)
-        with torch.cuda.device(X_pred.device), _timing.timed('pose_loss_fwd', X_pred.device):
-            _lib.check(getattr(_lib.lib(), 'mf_pose_loss_value_' + sfx)(
-                C.byref(desc), _lib.ptr(X_pred), _lib.ptr(R_pred), _lib.ptr(Xg), _lib.ptr(Rg), _lib.ptr(ts), _lib.ptr(near), _lib.ptr(partial),
-                _lib.ptr(_ticket(X_pred.device, cur)), _lib.ptr(out), _lib.ptr(gX), C.c_longlong(0 if gX is None else gX.numel()),
-                _lib.ptr(gR), C.c_longlong(0 if gR is None else gR.numel()), C.c_void_p(cur.cuda_stream)), 'mf_pose_loss_value')
+        ctx.desc = pose_loss_value(X_pred, R_pred, Xg, Rg, ts, near, gamma, _ticket(X_pred.device, torch.cuda.current_stream(X_pred.device)),
+                                   out, gX, gR)
         ctx.save_for_backward(X_pred, R_pred, Xg, Rg, ts, near)
         ctx.gX, ctx.gR = gX, gR
         ctx.set_materialize_grads(False)
-        ctx.desc, ctx.sfx = desc, sfx
         return out[0], out[1]
 
     @staticmethod
     def backward(ctx, gloss, grot):
-        import ctypes as C
-        from . import _lib, _timing
         none = (None,) * 7
         X_pred, R_pred, Xg, Rg, ts, near = ctx.saved_tensors
         # a None upstream is a zero for that half: its gradient is not formed at all
@@ -368,11 +378,7 @@ class _FusedPoseLoss(torch.autograd.Function):
         if gloss is None or grot is None:
             zero = torch.zeros((), dtype=X_pred.dtype, device=X_pred.device)
         gl = torch.stack([(zero if g is None else g.to(X_pred.dtype).reshape(())) for g in (gloss, grot)])
-        stream = C.c_void_p(torch.cuda.current_stream(X_pred.device).cuda_stream)
-        with torch.cuda.device(X_pred.device), _timing.timed('pose_loss_bwd', X_pred.device):
-            _lib.check(getattr(_lib.lib(), 'mf_pose_loss_bwd_' + ctx.sfx)(
-                C.byref(ctx.desc), _lib.ptr(X_pred), _lib.ptr(R_pred), _lib.ptr(Xg), _lib.ptr(Rg), _lib.ptr(ts), _lib.ptr(near), _lib.ptr(gl),
-                _lib.ptr(gX), _lib.ptr(gR), stream), 'mf_pose_loss_bwd')
+        pose_loss_backward(ctx.desc, X_pred, R_pred, Xg, Rg, ts, near, gl, gX, gR)
         return (gX, gR) + none[2:]
 
 

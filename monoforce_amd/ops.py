@@ -42,14 +42,15 @@ are int32 [1] on the device.
 its input is None; `costs` [B] = base_costs + w_map map + w_path xtrack, `terms` [B,2] = (map, xtrack).  One launch.
 
 The rollout ops and `DPhysics`'s own autograd function (monoforce_amd/dphysics.py: more options -- articulated bodies, path costs,
-strided controls) launch through the same marshalling (monoforce_amd/rollout_launch.py); `rollout()` / `splat()` below are the
-functional entries.
+strided controls) launch through the same marshalling (monoforce_amd/rollout_launch.py), the splat ops and `voxel_pooling` likewise
+(monoforce_amd/splat.py); only the MPPI and pose-cost entry points, which have no other caller, are marshalled here (`_lib.launch`).
+`rollout()` / `splat()` below are the functional entries.
 """
 import ctypes as C
 
 import torch
 
-from . import _lib, _timing, rollout_launch as rl
+from . import _lib, rollout_launch as rl, splat as _splat
 
 
 class _PoolOwner:       # the registered ops have no module to hang the persistent gradient-copy pools on
@@ -76,18 +77,6 @@ _L.define('path_costs(Tensor cost_rows, Tensor? force_cost, Tensor x_last, Tenso
 _L.define('mppi_update(Tensor costs, Tensor controls, Tensor nominal, float lam) -> (Tensor, Tensor, Tensor, Tensor)')
 _L.define('pose_costs(Tensor Xs, Tensor Rs, Tensor points, Tensor? cost_map, Tensor? path, Tensor? base_costs, float grid_res, float d_max, '
           'float lethal, float off_map, float[] weights) -> (Tensor, Tensor)')
-
-
-def _sfx(dtype):
-    if dtype == torch.float32:
-        return 'f32'
-    if dtype == torch.float64:
-        return 'f64'
-    raise TypeError(f'monoforce ops compute in float32 or float64, got {dtype}')
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _time_grid(consts, T, dt, dev):
@@ -189,48 +178,19 @@ def _rollout_bwd_fake(z, mu, controls, x_init, xd0, R0, w0, pts, part_id, Iinv, 
 
 
 # ---- BEV voxel pooling -------------------------------------------------------------------------------------------------
-def _splat_desc(B, n_per_sample, Cc, dx, bx, nx):
-    off = (torch.tensor(bx, dtype=torch.float32) - torch.tensor(dx, dtype=torch.float32) / 2.).tolist()      # float32, like lss.py:246
-    return _lib.MfSplatDesc(B=B, n_per_sample=n_per_sample, C=Cc, nx=int(nx[0]), ny=int(nx[1]), nz=int(nx[2]),
-                            off=(C.c_float * 3)(*off), dx=(C.c_float * 3)(*[float(v) for v in dx]))
-
-
 @torch.library.impl(_L, 'bev_splat_plan', 'CUDA')
 def _splat_plan(geom, dx, bx, nx):
-    B = geom.shape[0]
-    g = geom.detach().to(torch.float32).contiguous().view(-1, 3)
-    d = _splat_desc(B, g.shape[0] // B, 1, dx, bx, nx)
-    nbytes = _lib.lib().mf_bev_splat_workspace_bytes(C.byref(d))
-    if nbytes == 0:
-        raise RuntimeError('mf_bev_splat_workspace_bytes: ' + _lib.lib().mf_last_error().decode())
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=geom.device)
-    with torch.cuda.device(geom.device), _timing.timed('splat_prepare', geom.device):
-        _lib.check(_lib.lib().mf_bev_splat_prepare(C.byref(d), _lib.ptr(g), _lib.ptr(ws), _stream(geom.device)), 'mf_bev_splat_prepare')
-    return ws
+    return _splat.SplatPlan(geom, dx, bx, nx).workspace
 
 
 @torch.library.impl(_L, 'bev_splat_fwd', 'CUDA')
 def _splat_fwd(x, plan, B, n_per_sample, dx, bx, nx):
-    Cc = x.shape[-1]
-    xf = x.contiguous().view(-1, Cc)
-    assert xf.shape[0] == B * n_per_sample, 'features and plan disagree on the number of points'
-    d = _splat_desc(B, n_per_sample, Cc, dx, bx, nx)
-    out = torch.empty(B, d.nz * Cc, d.nx, d.ny, dtype=xf.dtype, device=xf.device)
-    with torch.cuda.device(xf.device), _timing.timed('splat_fwd_kernel', xf.device):
-        _lib.check(getattr(_lib.lib(), 'mf_bev_splat_fwd_' + _sfx(xf.dtype))(C.byref(d), _lib.ptr(xf), _lib.ptr(plan), _lib.ptr(out), _stream(xf.device)),
-                   'mf_bev_splat_fwd')
-    return out
+    return _splat.pool_forward(x, _splat.SplatPlan.wrap(plan, B, n_per_sample, _splat.grid_host(dx, bx, nx)))
 
 
 @torch.library.impl(_L, 'bev_splat_bwd', 'CUDA')
 def _splat_bwd(grad, plan, B, n_per_sample, Cc, dx, bx, nx):
-    g = grad.contiguous()
-    d = _splat_desc(B, n_per_sample, Cc, dx, bx, nx)
-    gx = torch.empty(B * n_per_sample, Cc, dtype=g.dtype, device=g.device)
-    with torch.cuda.device(g.device), _timing.timed('splat_bwd_kernel', g.device):
-        _lib.check(getattr(_lib.lib(), 'mf_bev_splat_bwd_' + _sfx(g.dtype))(C.byref(d), _lib.ptr(g), _lib.ptr(plan), _lib.ptr(gx), _stream(g.device)),
-                   'mf_bev_splat_bwd')
-    return gx
+    return _splat.pool_backward(grad, _splat.SplatPlan.wrap(plan, B, n_per_sample, _splat.grid_host(dx, bx, nx)), Cc)
 
 
 def _splat_setup(ctx, inputs, output):
@@ -280,8 +240,7 @@ def _mppi_perturb(nominal, noise, sigma, lo, hi, keep_nominal):
         f'noise must be [B,T,2] and nominal [T,2], got {tuple(nz.shape)} and {tuple(nom.shape)}'
     d = _mppi_desc(nz.shape[0], nz.shape[1], sigma=sigma, lo=lo, hi=hi, keep_nominal=keep_nominal)
     controls = torch.empty_like(nz)
-    with torch.cuda.device(nz.device), _timing.timed('mppi_perturb_kernel', nz.device):
-        _lib.check(_lib.lib().mf_mppi_perturb_f32(C.byref(d), _lib.ptr(nom), _lib.ptr(nz), _lib.ptr(controls), _stream(nz.device)), 'mf_mppi_perturb')
+    _lib.launch('mf_mppi_perturb', nz.device, d, nom, nz, controls, dtype=torch.float32, timer='mppi_perturb_kernel')
     return controls
 
 
@@ -304,9 +263,7 @@ def _path_costs(cost_rows, force_cost, x_last, goal, weights):
     d = _mppi_desc(B, T, weights=weights)
     d.row_stride_b, d.row_stride_t, d.x_stride_b = rows.stride(0), rows.stride(1), xl.stride(0)
     costs, terms = torch.empty(B, dtype=torch.float32, device=rows.device), torch.empty(B, 3, dtype=torch.float32, device=rows.device)
-    with torch.cuda.device(rows.device), _timing.timed('path_costs_kernel', rows.device):
-        _lib.check(_lib.lib().mf_path_costs_f32(C.byref(d), _lib.ptr(rows), _lib.ptr(fc), _lib.ptr(xl), _lib.ptr(g), _lib.ptr(costs), _lib.ptr(terms),
-                                                _stream(rows.device)), 'mf_path_costs')
+    _lib.launch('mf_path_costs', rows.device, d, rows, fc, xl, g, costs, terms, dtype=torch.float32, timer='path_costs_kernel')
     return costs, terms
 
 
@@ -320,16 +277,13 @@ def mppi_update_into(costs, controls, nominal, lam, out):
     B, T = u.shape[:2]
     dev = u.device
     d = _mppi_desc(B, T, lam=lam)
-    nbytes = int(_lib.lib().mf_mppi_scratch_bytes(C.byref(d)))
-    if nbytes < 0:
-        raise RuntimeError('mf_mppi_scratch_bytes: ' + _lib.lib().mf_last_error().decode())
+    nbytes = _lib.size_query('mf_mppi_scratch_bytes', d)
     scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
     weights = torch.empty(B, dtype=torch.float32, device=dev)
     flags = torch.empty(2, dtype=torch.int32, device=dev)
     best, n_valid = flags[:1], flags[1:]
-    with torch.cuda.device(dev), _timing.timed('mppi_update_kernel', dev):
-        _lib.check(_lib.lib().mf_mppi_update_f32(C.byref(d), _lib.ptr(c), _lib.ptr(u), _lib.ptr(nom), _lib.ptr(weights), _lib.ptr(out), _lib.ptr(best),
-                                                 _lib.ptr(n_valid), _lib.ptr(scratch), C.c_longlong(nbytes), _stream(dev)), 'mf_mppi_update')
+    _lib.launch('mf_mppi_update', dev, d, c, u, nom, weights, out, best, n_valid, scratch, C.c_longlong(nbytes), dtype=torch.float32,
+                timer='mppi_update_kernel')
     return out, weights, best, n_valid
 
 
@@ -391,9 +345,7 @@ def pose_costs_into(Xs, Rs, points, cost_map, path, base_costs, grid_res, d_max,
                             grid_res=float(grid_res), d_max=float(d_max), lethal=float(lethal), off_map=float(off_map),
                             w_map=float(weights[0]), w_path=float(weights[1]))
     terms = torch.empty(B, 2, dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device), _timing.timed('pose_costs_kernel', x.device):
-        _lib.check(_lib.lib().mf_pose_costs_f32(C.byref(d), _lib.ptr(x), _lib.ptr(r), _lib.ptr(pts), _lib.ptr(cm), _lib.ptr(pa), _lib.ptr(base),
-                                                _lib.ptr(out), _lib.ptr(terms), _stream(x.device)), 'mf_pose_costs')
+    _lib.launch('mf_pose_costs', x.device, d, x, r, pts, cm, pa, base, out, terms, dtype=torch.float32, timer='pose_costs_kernel')
     return out, terms
 
 

@@ -1,13 +1,15 @@
-"""The rollout's two C-ABI calls, `mf_rollout_fwd_*` and `mf_rollout_bwd_*` (include/monoforce_hip.h), marshalled in ONE place.
+"""Every `mf_rollout_*` entry point of the C ABI (include/monoforce_hip.h), marshalled in ONE place.
 
 Everything that builds an `MfRolloutDesc`, `MfRolloutFwdBufs`, `MfRolloutBwdBufs` or `MfRolloutLoss`, or that calls the rollout
-launches, their sizing queries (`mf_rollout_force_stride`, `mf_rollout_record_bytes[_f64]`) and the reduction over the gradient copies
-(`mf_reduce_grad_copies_*`), is here; a new buffer or descriptor field is threaded through this file alone.  The callers --
-`DPhysics` (dphysics.py, dphysics_bwd.py) and the registered ops (ops.py) -- decide WHAT they want (options, gradient-copy count,
-which outputs) and shape what they hand out (transposes, `[:N]` slices); nothing here knows who calls.
+launches (`mf_rollout_fwd_*`, `mf_rollout_bwd_*`, `mf_rollout_default_state_*`), their sizing and policy queries
+(`mf_rollout_force_stride`, `mf_rollout_record_bytes[_f64]`, `mf_rollout_loss_fusable`, `mf_rollout_bwd_window`,
+`mf_rollout_bwd_wants_gcontrols`, `mf_rollout_fwd_stages_zmu`) and the reduction over the gradient copies
+(`mf_reduce_grad_copies_*`), is here; a new buffer or descriptor field is threaded through this file alone.  The launches go through
+`_lib.launch`.  The callers -- `DPhysics` (dphysics.py, dphysics_bwd.py) and the registered ops (ops.py) -- decide WHAT they want
+(options, gradient-copy count, which outputs) and shape what they hand out (transposes, `[:N]` slices); nothing here knows who calls.
 
-`launch_forward` / `launch_backward` run with the tensors' device CURRENT: the library's policy queries read the CU count of the
-current device, so a caller enters `torch.cuda.device` once around its whole launch path.
+The queries read the CU count of the CURRENT device, so a caller enters `torch.cuda.device` once around its whole launch
+path, queries included.
 
 Imports without a GPU (the library is loaded at the first launch); `canonical_maps` and `time_grid` are plain torch.
 """
@@ -18,18 +20,6 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib, _timing
-
-
-def scalar_suffix(dtype):
-    if dtype == torch.float32:
-        return 'f32'
-    if dtype == torch.float64:
-        return 'f64'
-    raise TypeError(f'DPhysics computes in float32 or float64, got {dtype}')
-
-
-def stream_ptr(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -139,9 +129,10 @@ class GradPool:
         # ONE collective on this buffer, no pack / unpack (train.py::TerrainFitProblem)
         flat = torch.empty(self.n_maps * self.n + 1, dtype=self.buf.dtype, device=self.buf.device)
         out = flat[:-1].view((self.n_maps,) + tuple(map_shape))
-        fn = getattr(_lib.lib(), 'mf_reduce_grad_copies_' + scalar_suffix(self.buf.dtype))
-        _lib.check(fn(_lib.ptr(self.buf), self.n_maps, self.copies, C.c_longlong(self.n), _lib.ptr(out),
-                      C.c_void_p(self.stream)), 'mf_reduce_grad_copies')
+        # (a direct call, not `_lib.launch`: the reduction goes on the stream taken at `acquire` -- the one the scatter ran on --, not the current one)
+        fn = getattr(_lib.lib(), 'mf_reduce_grad_copies_' + _lib.scalar_suffix(self.buf.dtype))
+        _lib.check(fn(*_lib.c_args(self.buf, self.n_maps, self.copies, C.c_longlong(self.n), out), C.c_void_p(self.stream)),
+                   'mf_reduce_grad_copies')
         if not torch.cuda.is_current_stream_capturing():
             if self.done is None:
                 self.done = torch.cuda.Event()
@@ -190,6 +181,33 @@ def record_bytes(desc, dtype):
     return int(rb(C.byref(desc)))
 
 
+def loss_fusable(desc):
+    """Which launches of `desc` can carry physics_loss themselves: one of the MF_LOSS_FUSE_* answers of _lib.py."""
+    return int(_lib.lib().mf_rollout_loss_fusable(C.byref(desc)))
+
+
+def bwd_window(desc):
+    """True if the backward of `desc` sends its cell gradients through per-workgroup LDS windows (saturated positions-only launches)."""
+    return bool(_lib.lib().mf_rollout_bwd_window(C.byref(desc)))
+
+
+def bwd_wants_gcontrols(desc):
+    """True if the backward kernels chosen for `desc` cannot leave the control gradient out."""
+    return bool(_lib.lib().mf_rollout_bwd_wants_gcontrols(C.byref(desc)))
+
+
+def fwd_stages_zmu(desc):
+    """True if the forward of `desc` fills `zmu_scratch` with the interleaved (z, mu) pair: its backward may read it as `zmu`."""
+    return bool(_lib.lib().mf_rollout_fwd_stages_zmu(C.byref(desc)))
+
+
+def default_state(controls, x, xd, R, w):
+    """One `mf_rollout_default_state_*` launch: the start state of contiguous `controls` [B,T,2] (x = 0, xd = (v_0, 0, 0), R = I,
+    omega = (0, 0, w_0)) written into the four buffers."""
+    _lib.launch('mf_rollout_default_state', controls.device, C.c_int32(x.shape[0]), C.c_int32(controls.shape[1]), controls, x, xd, R, w,
+                dtype=controls.dtype)
+
+
 class ForwardBufs(NamedTuple):
     """What one forward launch wrote, in the descriptor's layout and at the kernel's force stride; None = not asked for."""
     Xs: torch.Tensor
@@ -234,9 +252,7 @@ def launch_forward(desc, z, mu, controls, ts, points, part, state, *, want_force
         Xs=p(out.Xs), Xds=p(out.Xds), Rs=p(out.Rs), Omegas=p(out.Om), Fs=p(out.Fs), Ff=p(out.Ff), Xraw=p(out.Xraw),
         joint_angles=p(joint_angles), cost_rows=p(out.cost_rows), path_cost=p(out.path_cost), zmu_scratch=p(zmu_scratch), zmu=p(zmu),
         rec=p(out.rec), loss=None if loss is None else C.addressof(loss))       # (`loss` stays alive until the call below returns)
-    fn = getattr(_lib.lib(), 'mf_rollout_fwd_' + scalar_suffix(dt))
-    with _timing.timed('rollout_fwd_kernel', dev):
-        _lib.check(fn(C.byref(desc), C.byref(bufs), stream_ptr(dev)), 'mf_rollout_fwd')
+    _lib.launch('mf_rollout_fwd', dev, desc, bufs, dtype=dt, timer='rollout_fwd_kernel')
     _timing.note_launch('rollout_fwd_kernel')
     return out
 
@@ -290,9 +306,7 @@ def launch_backward(desc, z, mu, controls, ts, points, part, state, saved, ups, 
         gz=p(gz), gmu=p(gmu), gcontrols=p(gcontrols), gx0=p(gx0), gxd0=p(gxd0), gR0=p(gR0), gw0=p(gw0),
         joint_angles=p(joint_angles), gjoint_angles=p(gja), rec=p(rec), zmu_scratch=p(zmu_scratch), zmu=p(zmu),
         loss=None if loss is None else C.addressof(loss))
-    fn = getattr(_lib.lib(), 'mf_rollout_bwd_' + scalar_suffix(dt))
-    with _timing.timed('rollout_bwd_kernel', dev):
-        _lib.check(fn(C.byref(desc), C.byref(bufs), stream_ptr(dev)), 'mf_rollout_bwd')
+    _lib.launch('mf_rollout_bwd', dev, desc, bufs, dtype=dt, timer='rollout_bwd_kernel')
     _timing.note_launch('rollout_bwd_kernel')
     if desc.map_shared:
         summed = pool.reduce(z.shape)          # one launch: both maps summed over their copies, the pool left zeroed

@@ -3,28 +3,27 @@
 
 `SplatPlan` is the geometry-only part (voxel keys + CSR lists); it is built once per `geom` and shared by forward and
 backward, and can be reused across steps while the camera calibration / augmentation is unchanged.
+
+Every `mf_bev_*` entry point of the C ABI is marshalled here and nowhere else (through `_lib.launch`): the plan's three `prepare`
+forms in `SplatPlan`, the two pooling launches in `pool_forward` / `pool_backward` -- which `_Pool` and the registered ops
+(ops.py, over `SplatPlan.wrap`) both call -- and the fused lift in `_LiftPool`.
 """
 import ctypes as C
+import os as _os
 
 import torch
 
-from . import _lib, _timing
+from . import _lib
 
-
-import os as _os
 _HOST_INVERSE = bool(int(_os.environ.get('MF_SPLAT_HOST_INVERSE', '0')))      # round 4's plan route for camera rigs (torch.inverse on the device)
 
 
-def _stream_ptr(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def grid_host(dx, bx, nx):
-    """(off, dx, n) of the BEV grid as host values (a device -> host read: a stream sync, not capturable in a hipGraph --
-    callers that build plans per frame read it once and pass it as `grid=`)."""
-    dxc, bxc = dx.detach().float().cpu(), bx.detach().float().cpu()
+    """(off, dx, n) of the BEV grid as host values; dx, bx, nx: tensors (a device -> host read: a stream sync, not capturable in a
+    hipGraph -- callers that build plans per frame read it once and pass it as `grid=`) or host sequences (the ops' schema)."""
+    dxc, bxc = (torch.as_tensor(t, dtype=torch.float32).detach().cpu() for t in (dx, bx))
     off = bxc - dxc / 2.                                        # float32, like lss.py:246
-    return off.tolist(), dxc.tolist(), [int(v) for v in nx.detach().cpu().tolist()]
+    return off.tolist(), dxc.tolist(), [int(v) for v in torch.as_tensor(nx).detach().cpu().tolist()]
 
 
 class SplatPlan:
@@ -42,34 +41,40 @@ class SplatPlan:
             rig = isinstance(cams, (tuple, list))
             _lib.require_hip_tensor(cams[0] if rig else cams, 'camera models')
             device, n_per_sample = (cams[0] if rig else cams).device, ((cams[0] if rig else cams).shape[0] // B) * frustum.shape[0]
-        off, dxl, n = grid if grid is not None else grid_host(dx, bx, nx)
-        self.B, self.n_per_sample = B, n_per_sample
-        self.nx, self.ny, self.nz = n
-        self.device = device
-        self._desc_args = dict(B=B, n_per_sample=self.n_per_sample, nx=n[0], ny=n[1], nz=n[2],
-                               off=(C.c_float * 3)(*off), dx=(C.c_float * 3)(*dxl))
+        self._set(None, B, n_per_sample, grid if grid is not None else grid_host(dx, bx, nx))
         d = self.desc(1)
-        nbytes = _lib.lib().mf_bev_splat_workspace_bytes(C.byref(d))
-        if nbytes == 0:
-            raise RuntimeError('mf_bev_splat_workspace_bytes: ' + _lib.lib().mf_last_error().decode())
+        nbytes = _lib.size_query('mf_bev_splat_workspace_bytes', d)
         if workspace is not None and workspace.numel() >= nbytes and workspace.device == device and workspace.dtype == torch.uint8:
             self.workspace = workspace
         else:
             self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        with torch.cuda.device(device), _timing.timed('splat_prepare', device):
-            if _cameras is None:
-                _lib.check(_lib.lib().mf_bev_splat_prepare(C.byref(d), _lib.ptr(g), _lib.ptr(self.workspace), _stream_ptr(device)),
-                           'mf_bev_splat_prepare')
-                self._keepalive = g
-            elif rig:
-                _lib.check(_lib.lib().mf_bev_splat_prepare_rig(C.byref(d), _lib.ptr(frustum), C.c_int32(frustum.shape[0]), *(_lib.ptr(t) for t in cams),
-                                                               _lib.ptr(self.workspace), _stream_ptr(device)), 'mf_bev_splat_prepare_rig')
-                self._keepalive = (frustum, cams)
-            else:
-                _lib.check(_lib.lib().mf_bev_splat_prepare_cameras(C.byref(d), _lib.ptr(frustum), C.c_int32(frustum.shape[0]),
-                                                                   _lib.ptr(cams), _lib.ptr(self.workspace), _stream_ptr(device)),
-                           'mf_bev_splat_prepare_cameras')
-                self._keepalive = (frustum, cams)
+        if _cameras is None:
+            _lib.launch('mf_bev_splat_prepare', device, d, g, self.workspace, timer='splat_prepare')
+            self._keepalive = g
+        elif rig:
+            _lib.launch('mf_bev_splat_prepare_rig', device, d, frustum, C.c_int32(frustum.shape[0]), *cams, self.workspace, timer='splat_prepare')
+            self._keepalive = (frustum, cams)
+        else:
+            _lib.launch('mf_bev_splat_prepare_cameras', device, d, frustum, C.c_int32(frustum.shape[0]), cams, self.workspace, timer='splat_prepare')
+            self._keepalive = (frustum, cams)
+
+    def _set(self, workspace, B, n_per_sample, grid):
+        off, dxl, n = grid
+        self.workspace, self.B, self.n_per_sample = workspace, B, n_per_sample
+        self.nx, self.ny, self.nz = n
+        self._desc_args = dict(B=B, n_per_sample=n_per_sample, nx=n[0], ny=n[1], nz=n[2], off=(C.c_float * 3)(*off), dx=(C.c_float * 3)(*dxl))
+
+    @classmethod
+    def wrap(cls, workspace, B, n_per_sample, grid):
+        """The plan that an earlier `SplatPlan` of this shape and `grid` (= `grid_host(...)`) built in `workspace`: what the registered
+        ops, whose plan is that bare tensor, hand to `pool_forward` / `pool_backward`."""
+        plan = cls.__new__(cls)
+        plan._set(workspace, B, n_per_sample, grid)
+        return plan
+
+    @property
+    def device(self):
+        return self.workspace.device
 
     @classmethod
     def from_cameras(cls, frustum, rots, trans, intrins, post_rots, post_trans, dx, bx, nx, grid=None, host_inverse=None, workspace=None):
@@ -103,32 +108,33 @@ class SplatPlan:
         return _lib.MfSplatDesc(C=C_, **self._desc_args)
 
 
+def pool_forward(x, plan):
+    """x [..., C], one row per point of `plan` -> [B, C*nz, nx, ny]: one `mf_bev_splat_fwd_*` launch."""
+    Cc = x.shape[-1]
+    xf = x.contiguous().view(-1, Cc)
+    assert xf.shape[0] == plan.B * plan.n_per_sample, 'features and plan disagree on the number of points'
+    out = torch.empty(plan.B, plan.nz * Cc, plan.nx, plan.ny, dtype=xf.dtype, device=xf.device)
+    _lib.launch('mf_bev_splat_fwd', xf.device, plan.desc(Cc), xf, plan.workspace, out, dtype=xf.dtype, timer='splat_fwd_kernel')
+    return out
+
+
+def pool_backward(gout, plan, Cc):
+    """Gradient [B, C*nz, nx, ny] of `pool_forward`'s result -> that of its point rows, [B * n_per_sample, C]: one `mf_bev_splat_bwd_*` launch."""
+    g = gout.contiguous()
+    gx = torch.empty(plan.B * plan.n_per_sample, Cc, dtype=g.dtype, device=g.device)
+    _lib.launch('mf_bev_splat_bwd', g.device, plan.desc(Cc), g, plan.workspace, gx, dtype=g.dtype, timer='splat_bwd_kernel')
+    return gx
+
+
 class _Pool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, plan):
-        Cc = x.shape[-1]
-        xf = x.contiguous().view(-1, Cc)
-        assert xf.shape[0] == plan.B * plan.n_per_sample, 'features and geometry disagree on the number of points'
-        sfx = {torch.float32: 'f32', torch.float64: 'f64'}[xf.dtype]
-        out = torch.empty(plan.B, plan.nz * Cc, plan.nx, plan.ny, dtype=xf.dtype, device=xf.device)
-        d = plan.desc(Cc)
-        with torch.cuda.device(xf.device), _timing.timed('splat_fwd_kernel', xf.device):
-            _lib.check(getattr(_lib.lib(), 'mf_bev_splat_fwd_' + sfx)(C.byref(d), _lib.ptr(xf), _lib.ptr(plan.workspace),
-                                                                       _lib.ptr(out), _stream_ptr(xf.device)), 'mf_bev_splat_fwd')
-        ctx.plan, ctx.x_shape, ctx.sfx = plan, x.shape, sfx
-        return out
+        ctx.plan, ctx.x_shape = plan, x.shape
+        return pool_forward(x, plan)
 
     @staticmethod
     def backward(ctx, gout):
-        plan = ctx.plan
-        Cc = ctx.x_shape[-1]
-        g = gout.contiguous()
-        gx = torch.empty(plan.B * plan.n_per_sample, Cc, dtype=g.dtype, device=g.device)
-        d = plan.desc(Cc)
-        with torch.cuda.device(g.device), _timing.timed('splat_bwd_kernel', g.device):
-            _lib.check(getattr(_lib.lib(), 'mf_bev_splat_bwd_' + ctx.sfx)(C.byref(d), _lib.ptr(g), _lib.ptr(plan.workspace),
-                                                                           _lib.ptr(gx), _stream_ptr(g.device)), 'mf_bev_splat_bwd')
-        return gx.view(ctx.x_shape), None
+        return pool_backward(gout, ctx.plan, ctx.x_shape[-1]).view(ctx.x_shape), None
 
 
 class _LiftPool(torch.autograd.Function):
@@ -141,17 +147,14 @@ class _LiftPool(torch.autograd.Function):
         Cc = context.shape[1]
         assert context.shape == (BN, Cc, fH, fW) and BN * D * fH * fW == plan.B * plan.n_per_sample, \
             'depth / context and the geometry disagree on the number of frustum points'
-        sfx = {torch.float32: 'f32', torch.float64: 'f64'}[depth.dtype]
         dep = depth.contiguous()
         ctxT = context.to(depth.dtype).permute(0, 2, 3, 1).contiguous()          # pixel-major rows [BN, fH, fW, C] (0.5 MB per sample)
         d = plan.desc(Cc)
         d.lift_D, d.lift_hw = D, fH * fW
         out = torch.empty(plan.B, plan.nz * Cc, plan.nx, plan.ny, dtype=dep.dtype, device=dep.device)
-        with torch.cuda.device(dep.device), _timing.timed('lift_splat_fwd_kernel', dep.device):
-            _lib.check(getattr(_lib.lib(), 'mf_bev_lift_splat_fwd_' + sfx)(C.byref(d), _lib.ptr(dep), _lib.ptr(ctxT), _lib.ptr(plan.workspace),
-                                                                            _lib.ptr(out), _stream_ptr(dep.device)), 'mf_bev_lift_splat_fwd')
+        _lib.launch('mf_bev_lift_splat_fwd', dep.device, d, dep, ctxT, plan.workspace, out, dtype=dep.dtype, timer='lift_splat_fwd_kernel')
         ctx.save_for_backward(dep, ctxT)
-        ctx.plan, ctx.d, ctx.sfx = plan, d, sfx
+        ctx.plan, ctx.d = plan, d
         return out
 
     @staticmethod
@@ -161,10 +164,8 @@ class _LiftPool(torch.autograd.Function):
         g = gout.contiguous()
         rows = torch.empty(plan.B * plan.nz * plan.nx * plan.ny, d.C, dtype=g.dtype, device=g.device)     # voxel-major gradient rows
         g_dep, g_ctx = torch.empty_like(dep), torch.empty_like(ctxT)
-        with torch.cuda.device(g.device), _timing.timed('lift_splat_bwd_kernel', g.device):
-            _lib.check(getattr(_lib.lib(), 'mf_bev_lift_splat_bwd_' + ctx.sfx)(
-                C.byref(d), _lib.ptr(dep), _lib.ptr(ctxT), _lib.ptr(plan.workspace), _lib.ptr(g), _lib.ptr(rows), _lib.ptr(g_dep),
-                _lib.ptr(g_ctx), _stream_ptr(g.device)), 'mf_bev_lift_splat_bwd')
+        _lib.launch('mf_bev_lift_splat_bwd', g.device, d, dep, ctxT, plan.workspace, g, rows, g_dep, g_ctx, dtype=dep.dtype,
+                    timer='lift_splat_bwd_kernel')
         return g_dep, g_ctx.permute(0, 3, 1, 2), None
 
 

@@ -6,17 +6,11 @@ rollout reads the two pooled maps.  `stage_terrain` is those steps as ONE kernel
 full-resolution `terrain` (the height-map loss needs it), the pooled `z` and `mu` -- and leaves the interleaved `(z, mu)`
 pair the rollout kernels gather from attached to `z`, where `DPhysics` finds it and skips its own interleave pass.
 """
-import ctypes as C
-
 import torch
 
-from . import _lib, _timing
+from . import _lib
 
 __all__ = ['stage_terrain', 'staged_pair']
-
-
-def _stream_ptr(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 class _Stage(torch.autograd.Function):
@@ -30,9 +24,7 @@ class _Stage(torch.autograd.Function):
         mu = torch.empty_like(z)
         zmu = torch.empty(B, h, w, 2, dtype=torch.float32, device=dev)
         desc = _lib.MfStageDesc(B=B, H=H, W=W, k=k)
-        with torch.cuda.device(dev), _timing.timed('terrain_stage_fwd', dev):
-            _lib.check(_lib.lib().mf_terrain_stage_fwd_f32(C.byref(desc), _lib.ptr(geom), _lib.ptr(diff), _lib.ptr(friction), _lib.ptr(terrain),
-                                                           _lib.ptr(z), _lib.ptr(mu), _lib.ptr(zmu), _stream_ptr(dev)), 'mf_terrain_stage_fwd')
+        _lib.launch('mf_terrain_stage_fwd', dev, desc, geom, diff, friction, terrain, z, mu, zmu, dtype=torch.float32, timer='terrain_stage_fwd')
         ctx.desc = desc
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(zmu)
@@ -47,9 +39,7 @@ class _Stage(torch.autograd.Function):
         dev = ref.device
         g_geom = torch.empty(desc.B, desc.H, desc.W, dtype=torch.float32, device=dev)
         g_diff, g_fric = torch.empty_like(g_geom), torch.empty_like(g_geom)
-        with torch.cuda.device(dev), _timing.timed('terrain_stage_bwd', dev):
-            _lib.check(_lib.lib().mf_terrain_stage_bwd_f32(C.byref(desc), _lib.ptr(g_terrain), _lib.ptr(gz), _lib.ptr(gmu), _lib.ptr(g_geom),
-                                                           _lib.ptr(g_diff), _lib.ptr(g_fric), _stream_ptr(dev)), 'mf_terrain_stage_bwd')
+        _lib.launch('mf_terrain_stage_bwd', dev, desc, g_terrain, gz, gmu, g_geom, g_diff, g_fric, dtype=torch.float32, timer='terrain_stage_bwd')
         return g_geom, g_diff, g_fric, None
 
 

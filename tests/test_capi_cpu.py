@@ -32,6 +32,79 @@ def test_library_exports_every_declared_symbol(built_lib):
     assert built_lib.mf_version().decode().startswith('monoforce_hip')
 
 
+def _base(name):
+    return re.sub(r'_f(32|64)$', '', name.rstrip('_'))
+
+
+def entry_points_named_by_module():
+    """{module file name: base names of the `mf_*` entry points its CODE names}, over monoforce_amd/*.py except _lib.py: attribute names
+    and string constants (the names handed to `_lib.launch` / `_lib.check` count) that start with `mf_`, a trailing `_f32` / `_f64`
+    stripped; docstrings and comments do not count."""
+    import ast
+    import glob
+    found = {}
+    for path in sorted(glob.glob(os.path.join(REPO, 'monoforce_amd', '*.py'))):
+        if os.path.basename(path) == '_lib.py':
+            continue
+        tree = ast.parse(open(path).read())
+        docstrings = set()
+        for node in ast.walk(tree):
+            if isinstance(node, (ast.Module, ast.ClassDef, ast.FunctionDef, ast.AsyncFunctionDef)) and node.body:
+                first = node.body[0]
+                if isinstance(first, ast.Expr) and isinstance(first.value, ast.Constant) and isinstance(first.value.value, str):
+                    docstrings.add(id(first.value))
+        names = set()
+        for node in ast.walk(tree):
+            if isinstance(node, ast.Attribute) and node.attr.startswith('mf_'):
+                names.add(_base(node.attr))
+            elif isinstance(node, ast.Constant) and isinstance(node.value, str) and node.value.startswith('mf_') and id(node) not in docstrings:
+                names.add(_base(node.value))
+        found[os.path.basename(path)] = names
+    return found
+
+
+def test_every_entry_point_is_marshalled_in_one_module():
+    """Each C-ABI entry point has its argument list written down in at most ONE module of monoforce_amd/ (none: it is C-side only), and
+    the families live where their docstrings say: the rollout in rollout_launch.py, the splat in splat.py, the losses in losses.py.
+    (The parent of the commit that added this test had ten violations: five names in two modules, five rollout names outside
+    rollout_launch.py.)"""
+    from monoforce_amd import _lib
+    found = entry_points_named_by_module()
+    homes = (('rollout_launch.py', ('mf_rollout_', 'mf_reduce_grad_copies')), ('splat.py', ('mf_bev_',)),
+             ('losses.py', ('mf_physics_loss_', 'mf_pose_loss_', 'mf_nearest_steps')))
+    assert all(home in found for home, _ in homes)
+    violations = []
+    for base in sorted({_base(s) for s in _lib.SYMBOLS} - {'mf_last_error', 'mf_last_launch'}):
+        users = sorted(m for m, names in found.items() if base in names)
+        if len(users) > 1:
+            violations.append(f'{base} is named in {users}')
+        for home, prefixes in homes:
+            if base.startswith(prefixes) and users and home not in users:
+                violations.append(f'{base} is named in {users}, not in {home}')
+    assert not violations, f'{len(violations)} violations:\n' + '\n'.join(violations)
+
+
+def test_c_args_conversion():
+    """`_lib.c_args`, the one place launch arguments become C values: tensor -> its data pointer, None -> NULL, a descriptor -> by
+    reference; ctypes scalars and arrays are handed on untouched."""
+    import torch
+    from monoforce_amd import _lib
+    t, d = torch.arange(6, dtype=torch.float32), _lib.MfStageDesc(B=1, H=2, W=3, k=1)
+    view = t[2:]
+    n32, n64, arr = ctypes.c_int32(7), ctypes.c_longlong(1 << 40), (ctypes.c_float * 3)(1., 2., 3.)
+    out = _lib.c_args(d, t, None, view, n32, n64, arr, 5)
+    assert len(out) == 8
+    assert out[0]._obj is d
+    assert isinstance(out[1], ctypes.c_void_p) and out[1].value == t.data_ptr()
+    assert out[2] is None
+    assert isinstance(out[3], ctypes.c_void_p) and out[3].value == view.data_ptr() == t.data_ptr() + 8
+    assert out[4] is n32 and out[5] is n64 and out[6] is arr and out[7] == 5
+    assert _lib.c_args() == []
+    assert _lib.scalar_suffix(torch.float32) == 'f32' and _lib.scalar_suffix(torch.float64) == 'f64'
+    with pytest.raises(TypeError, match='float32 or float64'):
+        _lib.scalar_suffix(torch.float16)
+
+
 def test_struct_layout_matches_header(built_lib):
     """ctypes mirrors must have the C struct sizes (checked against sizes the library reports)."""
     from monoforce_amd import _lib
