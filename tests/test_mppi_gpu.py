@@ -17,6 +17,13 @@ from tests import mppi_reference as ref
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 SHAPES = [(1, 1), (2, 3), (65, 41), (257, 120), (1030, 7)]      # partial wave, second workgroup, several 64-rollout chunks
+# The launch configurations beyond: path_costs_kernel runs S = 16 / 8 / 4 waves per 64-rollout group for B <= 8192 / <= 16384 / above (the
+# first three shapes: S = 8 with one rollout in the last group, S = 4 with T < S and with T < S on three of the four waves' second trip);
+# mppi_finish_kernel deals the ceil(B / 64) chunks to 16 waves, `per` chunks each: 129 chunks -> per = 9 (wave 14 takes 3 of 9, wave 15 none),
+# 257 -> per = 17 (wave 15 takes 2 of 17), 65 -> per = 5 (waves 13 .. 15 take none); T = 70: a second, partial 64-step tile.
+# tests/test_side_kernel_shapes_cpu.py holds these thresholds to the source.
+SHAPES += [(8193, 3), (16385, 2), (16385, 3), (4097, 70)]
+SHAPES += [(8193, 9), (16385, 5)]      # ... and S = 8, S = 4 with a step in every wave (above, most of the S partial sums are zeros) and a ragged second trip
 SIGMA, LO, HI = (0.3, 0.6), (-1.0, -2.0), (1.0, 2.0)
 
 

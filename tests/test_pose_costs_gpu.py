@@ -3,7 +3,8 @@ path): the kernel against the referee of tests/pose_costs_reference.py (pinned o
 determinism, isolation of a lethal rollout, the term switches, a real rollout, the planner stage by stage, its behaviour, capture, the shooter.
 
 Error bars as in tests/test_mppi_gpu.py: "rel-to-absmax" against the referee's float64 evaluation of the same float32 inputs, bar
-max(1e-5, 3 d32) with d32 the referee's own float32-to-float64 distance (1e-7 .. 3e-7 at the shapes here: the floor governs).  The sets of +inf
+max(1e-5, 3 d32) with d32 the referee's own float32-to-float64 distance (1e-7 .. 3e-7 at the shapes of pc.SHAPES: the floor governs; up to 4.3e-6 on the map term of pc.CONFIG_SHAPES, where the maximum
+over thousands of rollouts meets the worst rounding of the blend).  The sets of +inf
 costs must be EQUAL; the constructed inputs keep every discontinuous decision 1e-3 away from its threshold (tests/pose_costs_cases.py)."""
 import pytest
 import torch
@@ -78,6 +79,86 @@ def test_constructed_poses_match_the_referee(cases, shape):
         lethal = _check(costs, terms, _args(c), scalars, (0.7, 1.3), f'{shape} off_map={off_map}')
         if shape[0] >= 65:
             assert bool(lethal.any()) and not bool(lethal.all())      # both kinds occur, or the test shows nothing
+
+
+# ---- 1b. every launch configuration ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('shape', pc.CONFIG_SHAPES)
+def test_every_launch_configuration_matches_the_referee(shape):
+    """The workgroup shapes the host picks from B and N, and the trips of the pose loop beyond the first (pc.CONFIG_SHAPES says which shape
+    reaches what).  On the CPU the referee's float32 and float64 +inf sets are equal at every shape, both kinds of cost occur at every one
+    (1 .. 8091 lethal rollouts), and its own float32-to-float64 distance is at most 4.3e-6 (the map term at (8193, 3, 4)): the bar of the
+    file header, unchanged."""
+    c = pc.constructed(*shape)
+    print(f'{shape}: {c["redraws"]} poses redrawn')
+    for off_map in (INF, 1.5):
+        scalars = (pc.GRID_RES, pc.D_MAX, pc.LETHAL, off_map)
+        costs, terms = _op(*_args(c), *scalars, (0.7, 1.3))
+        lethal = _check(costs, terms, _args(c), scalars, (0.7, 1.3), f'{shape} off_map={off_map}')
+        assert bool(lethal.any()) and not bool(lethal.all())      # both kinds occur, or the test shows nothing
+
+
+def test_a_body_or_a_path_beyond_the_tables_is_refused():
+    """N = 1025 and P = 257 do not fit the LDS tables: an error from the entry point's checks (which run before the launch, see
+    tests/test_pose_costs_cpu.py), the one next to it still answers."""
+    c = pc.constructed(5, 9, 1024)
+    scalars = (pc.GRID_RES, pc.D_MAX, pc.LETHAL, INF)
+    a = dict(zip(('Xs', 'Rs', 'points', 'cost_map', 'path', 'base'), _args(c)))
+    with pytest.raises(RuntimeError, match='1024 footprint points'):
+        _op(*{**a, 'points': torch.cat([c['points'], c['points'][:1]])}.values(), *scalars, (0.7, 1.3))
+    with pytest.raises(RuntimeError, match='256 path vertices'):
+        _op(*{**a, 'path': pc.walk_path(257)}.values(), *scalars, (0.7, 1.3))
+    _check(*_op(*a.values(), *scalars, (0.7, 1.3)), tuple(a.values()), scalars, (0.7, 1.3), 'after the refusals')
+
+
+@pytest.mark.parametrize('P', pc.PATH_LENGTHS)
+@pytest.mark.parametrize('shape', pc.RECT_SHAPES)
+def test_paths_of_every_length(cases, shape, P):
+    """A path of one vertex, of one segment, and of 16, 17 and 255 segments (the 16-lane deal of the points kernel: one full trip, a second
+    trip of lane 0 alone, sixteen trips with the last one short), in both kernels: a random walk inside the map with one zero-length segment."""
+    c = cases[shape]
+    path = pc.walk_path(P)
+    assert tuple(path.shape) == (P, 2) and (P < 3 or int((path[1:] == path[:-1]).all(-1).sum()) == 1)
+    scalars = (pc.GRID_RES, pc.D_MAX, pc.LETHAL, 1.5)
+    for what, a, w in (('with the map', (c['Xs'], c['Rs'], c['points'], c['cost_map'], path, c['base']), (0.7, 1.3)),
+                       ('path only', (c['Xs'], c['Rs'], c['points'], None, path, None), (0.0, 1.0))):
+        costs, terms = _op(*a, *scalars, w)
+        _check(costs, terms, a, scalars, w, f'{shape} P={P} {what}')
+        assert float(terms[:, 1].min()) > 0
+
+
+@pytest.fixture(scope='module')
+def rect_cases():
+    return {s: pc.constructed(*s, map_shape=pc.RECT) for s in pc.RECT_SHAPES}
+
+
+@pytest.mark.parametrize('shape', pc.RECT_SHAPES)
+def test_a_map_that_is_not_square(rect_cases, shape):
+    """48 x 80 nodes, the lethal block at second-axis indices 52 .. 65: `sample_map` takes one bound and one clamp from H, the other bound, the
+    other clamp and the row stride from W, and on a square map any of them could be swapped unnoticed.  The referee with the swap applied,
+    float64 on the CPU, against the referee as it is -- (65, 5, 7) / (33, 3, 223), off_map = inf and 1.5:
+      bounds swapped   the +inf set differs in 12, 8 / 4, 5 rollouts; the map term of the rollouts finite in both moves by 0.53 / 0.43 (off_map = 1.5)
+      clamps swapped   8, 14 / 5, 14 rollouts; 6.2e-3 .. 4.8e-2
+      stride swapped   23, 32 / 11, 16 rollouts; 0.12 .. 0.22
+    where the test asks for EQUAL +inf sets and a map term within 1e-5."""
+    c = rect_cases[shape]
+    assert tuple(c['cost_map'].shape) == pc.RECT and float(c['cost_map'][:, 48:].max()) == 5.0 and float(c['cost_map'][:, :48].max()) < 1.0
+    for off_map in (INF, 1.5):
+        scalars = (pc.GRID_RES, pc.D_MAX, pc.LETHAL, off_map)
+        costs, terms = _op(*_args(c), *scalars, (0.7, 1.3))
+        lethal = _check(costs, terms, _args(c), scalars, (0.7, 1.3), f'{shape} on 48x80 off_map={off_map}')
+        assert bool(lethal.any()) and not bool(lethal.all())
+    # the cells a rollout reads, counted with the row stride W: raising one that only rollout b0 reads makes b0 lethal and no other
+    read = pc.cells_read(c, pc.RECT)
+    scalars = (pc.GRID_RES, pc.D_MAX, pc.LETHAL, INF)
+    costs, _ = _op(*_args(c), *scalars, (0.7, 1.3))
+    B = shape[0]
+    b0, cell = next((b, k) for b in range(B) if bool(torch.isfinite(costs[b]))
+                    for k in sorted(read[b]) if not any(k in read[o] for o in range(B) if o != b))
+    m = c['cost_map'].clone()
+    m.view(-1)[cell] = 100.0
+    got, _ = _op(c['Xs'], c['Rs'], c['points'], m, c['path'], c['base'], *scalars, (0.7, 1.3))
+    keep = torch.arange(B) != b0
+    assert float(got[b0]) == INF and torch.equal(got[keep], costs[keep])
 
 
 # ---- 2. layouts and determinism -----------------------------------------------------------------------------------------------------

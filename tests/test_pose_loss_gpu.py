@@ -60,8 +60,8 @@ def _aten64(p, gamma, wx=1.0, wr=1.0):
 def _check(got, want, dtype, what=''):
     (l, r, gX, gR), (l0, r0, gX0, gR0) = got, want
     figs = (_rel(l, l0), _rel(r, r0), hp.rel_err(gX, gX0), hp.rel_err(gR, gR0))
-    print(what, str(dtype), 'value %.3g %.3g gradient %.3g %.3g' % figs)
     bv, bg = BARS[dtype]
+    print(what, str(dtype), 'value err %.3g %.3g bar %.3g, gradient err %.3g %.3g bar %.3g' % (*figs[:2], bv, *figs[2:], bg))
     assert figs[0] <= bv and figs[1] <= bv and figs[2] <= bg and figs[3] <= bg, (what, figs)
 
 
@@ -102,9 +102,12 @@ def test_fused_pose_loss_on_time_major_views_with_duplicate_stamps(dtype):
 
 
 # ---- 3: the mean finished inside the launch, the ticket shared with the position-only loss ------------------------------------------------
-@pytest.mark.parametrize('B,T2', [(1, 1), (5, 50), (1024, 50), (3000, 7)])
+# (1311, 50): 257 blocks, the first grid at which the finishing loop makes a second trip (thread 0 alone); (9000, 23): 809 blocks, four trips
+@pytest.mark.parametrize('B,T2', [(1, 1), (5, 50), (1024, 50), (3000, 7), (1311, 50), (9000, 23)])
 def test_pose_loss_value_is_finished_inside_the_launch_and_reusable(B, T2):
-    from monoforce_amd.losses import physics_loss_fused
+    """Bar 2e-6 against the float64 ATen form, or three times the distance d32 of the float32 ATen form on the CPU from the same where that is
+    more (it is not at these shapes: d32 is printed next to the error)."""
+    from monoforce_amd.losses import physics_loss_aten, physics_loss_fused
     T1 = 2 * T2 + 3
     p = {k: (v.float().to(DEV) if v.is_floating_point() else v.to(DEV)) for k, v in _problem(B, T1, T2, B).items()}
     args = ([p['X'], None, p['R']], [p['Xgt'], None, p['Rgt']], None, p['gt_ts'])
@@ -115,8 +118,34 @@ def test_pose_loss_value_is_finished_inside_the_launch_and_reusable(B, T2):
         pairs.append((float(loss), float(rot)))
     assert len(set(pairs)) == 1 and len(set(singles)) == 1, (pairs, singles)
     l0, r0, _, _ = _aten64(p, 0.9)
-    print(B, T2, 'value %.3g %.3g position-only %.3g' % (_rel(pairs[0][0], l0), _rel(pairs[0][1], r0), _rel(singles[0], l0)))
-    assert _rel(pairs[0][0], l0) <= 2e-6 and _rel(pairs[0][1], r0) <= 2e-6 and _rel(singles[0], l0) <= 2e-6
+    c = {k: v.cpu() for k, v in p.items()}               # the float32 inputs, on the CPU
+    l32, r32 = physics_loss_aten([c['X'], None, c['R']], [c['Xgt'], None, c['Rgt']], None, c['gt_ts'], gamma=0.9, rotation_loss=True, nearest=c['near'])
+    bl, br = max(2e-6, 3 * _rel(l32, l0)), max(2e-6, 3 * _rel(r32, r0))
+    print(f'pose loss value {B}x{T2}: xyz err {_rel(pairs[0][0], l0):.3g} bar {bl:.3g} (d32 {_rel(l32, l0):.3g}); rot err {_rel(pairs[0][1], r0):.3g} bar {br:.3g} '
+          f'(d32 {_rel(r32, r0):.3g}); position-only err {_rel(singles[0], l0):.3g} bar {bl:.3g}')
+    assert _rel(pairs[0][0], l0) <= bl and _rel(pairs[0][1], r0) <= br and _rel(singles[0], l0) <= bl
+
+
+def test_pose_loss_gradients_on_time_major_views_of_a_batch_that_is_no_multiple_of_a_wave():
+    """B = 1311 = 20 x 64 + 31 rollouts x 50 stamps on the rollout's time-major buffers: the backward kernel maps thread t to rollout t % B, so a
+    wave straddles two stamps almost everywhere.  d/dXs and d/dRs of 3 loss + 0.5 loss_rot against the float64 ATen form, BARS as everywhere."""
+    from monoforce_amd.losses import physics_loss_fused
+    B, T2 = 1311, 50
+    p = {k: (v.float() if v.is_floating_point() else v) for k, v in _problem(B, 2 * T2 + 3, T2, 1311).items()}
+    want = _aten64(p, 0.9, 3.0, 0.5)
+    bX = p['X'].transpose(0, 1).contiguous().to(DEV).requires_grad_(True)
+    bR = p['R'].transpose(0, 1).contiguous().to(DEV).requires_grad_(True)
+    X, R = bX.transpose(0, 1), bR.transpose(0, 1)
+    assert X.stride() == (3, 3 * B, 1) and R.stride() == (9, 9 * B, 3, 1)
+    loss, rot = physics_loss_fused([X, None, R], [p['Xgt'].to(DEV), None, p['Rgt'].to(DEV)], None, p['gt_ts'].to(DEV), gamma=0.9,
+                                   nearest=p['near'].to(DEV), rotation_loss=True)
+    gX, gR = torch.autograd.grad(3.0 * loss + 0.5 * rot, (X, R))
+    _check((loss.detach(), rot.detach(), gX, gR), want, torch.float32, 'pose loss gradient 1311x50 time-major')
+    # ... and the position-only kernels on the same views
+    (gX1,) = torch.autograd.grad(physics_loss_fused([X], [p['Xgt'].to(DEV)], None, p['gt_ts'].to(DEV), gamma=0.9, nearest=p['near'].to(DEV)) * 3.0, (X,))
+    err = hp.rel_err(gX1, want[2])
+    print(f'position-only gradient 1311x50 time-major: err {err:.3g} bar {BARS[torch.float32][1]:.3g}')
+    assert err <= BARS[torch.float32][1]
 
 
 # ---- 4: which calls take the HIP route ----------------------------------------------------------------------------------------------------
