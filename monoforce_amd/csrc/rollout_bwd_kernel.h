@@ -1021,6 +1021,9 @@ __global__ void __launch_bounds__(WIN ? 512 : (G > 256 ? G : 256)) rollout_bwd_k
   }
 }
 
+// Instantiated mappings -- those plan_bwd can hand this launcher (profiles/rollout_kernels_reachable.txt,
+// tests/test_rollout_instances_cpu.py): every mapping of choose_lane_map for the rigid body, all but the 4-points-per-lane ones with
+// G < 64 for the articulated one, and no (64, 2) for the float32 fast-math kernels without carry-over.
 template <typename S, bool FAST, bool JOINTS = false, bool CARRY = true>
 int launch_rollout_bwd(const RolloutBwdArgs<S>& a, const BwdRoute& r, int integ, hipStream_t st) {
   const LaneMap m = r.m;
@@ -1034,7 +1037,11 @@ int launch_rollout_bwd(const RolloutBwdArgs<S>& a, const BwdRoute& r, int integ,
     else                                                                                                                           \
       MF_KLAUNCH((rollout_bwd_kernel<S, G_, P_, MF_INTEG_ODEINT_EULER, FAST, JOINTS, CARRY>), dim3(grid), dim3(block), 0, st, a);  \
   }
-  MF_CASE(4, 1) MF_CASE(8, 1) MF_CASE(16, 1) MF_CASE(32, 1) MF_CASE(64, 1) MF_CASE(64, 2) MF_CASE(64, 4) MF_CASE(64, 8)
+  MF_CASE(4, 1) MF_CASE(8, 1) MF_CASE(16, 1) MF_CASE(32, 1) MF_CASE(64, 1)
+  // (the float32 fast-math kernels without carry-over: choose_lane_map, rollout_route.hip, answers (64, 2) beyond two waves per SIMD only,
+  //  and from 3/4 of a wave per CU up plan_bwd takes kBwdCarry -- whatever the CU count: more than 4 rollouts per CU against fewer than 3/4)
+  if constexpr (CARRY || !FAST) { MF_CASE(64, 2) }
+  MF_CASE(64, 4) MF_CASE(64, 8)
   MF_CASE(128, 1) MF_CASE(256, 1) MF_CASE(512, 1)
   if constexpr (!JOINTS) {   // the 4-points-per-lane mappings are a tuning / test option of the rigid-body kernels
     MF_CASE(1, 4) MF_CASE(2, 4) MF_CASE(4, 4) MF_CASE(8, 4) MF_CASE(16, 4) MF_CASE(32, 4)

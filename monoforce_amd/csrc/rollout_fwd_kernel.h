@@ -1052,8 +1052,11 @@ static inline void touch_controls(const RolloutArgs<S>& a, int b0, int nb, hipSt
   hipLaunchKernelGGL((touch_lines_kernel<0>), dim3(2048), dim3(256), 0, st, reinterpret_cast<const float4*>(al), n16, reinterpret_cast<float4*>(const_cast<char*>(al)));
 }
 
-// Instantiated mappings: one point per lane (G = 4..64) and (64, 2/4/8) always; the 4-points-per-lane mappings with G < 64
-// only for the full-output rigid-body kernels (they are a tuning / test option, see choose_lane_map).
+// Instantiated mappings -- those the planner can hand this launcher, and no others (profiles/rollout_kernels_reachable.txt,
+// tests/test_rollout_instances_cpu.py): (128 / 256 / 512, 1), (64, 4) and (64, 8) for every kernel but the SPLIT / ZMU ones;
+// one point per lane inside a wave (G = 4..64) and (64, 2) for rigid bodies; the 4-points-per-lane mappings with G < 64 for the
+// kernels that write the forces (a tuning / test option of the rigid body, see choose_lane_map; the articulated body's only
+// mappings inside a wave).  The projected cost rows (COST = 2) exist for the default integrator alone.
 template <typename S, bool FAST, bool JOINTS = false, bool FORCES = true, int COST = 0, bool SPLIT = false, bool ZMU = false>
 int launch_rollout_fwd(const RolloutArgs<S>& a, const FwdRoute& r, int integ, hipStream_t st) {
   const LaneMap m = r.m;
@@ -1066,19 +1069,27 @@ int launch_rollout_fwd(const RolloutArgs<S>& a, const FwdRoute& r, int integ, hi
   const unsigned grid = (unsigned)(((long long)nb * m.G + block - 1) / block);
   if (nb >= r.touch_lo && nb <= r.touch_hi) touch_controls(a, b0, nb, st);
   launched = false;
+  // (COST = 2 is called for the default integrator only: rollout_fwd_cost.hip / rollout_fwd_zmu_fast.hip send dynamics(), whose rotation
+  //  cannot drift, to the COST = 1 kernels -- so it has no dynamics() instantiation)
 #define MF_CASE(G_, P_)                                                                                                                   \
   if (!launched && m.G == G_ && m.PPL == P_) {                                                                                             \
-    launched = true;                                                                                                                       \
-    if (integ == MF_INTEG_DYNAMICS)                                                                                                        \
-      MF_KLAUNCH((rollout_fwd_kernel<S, G_, P_, MF_INTEG_DYNAMICS, FAST, JOINTS, FORCES, COST, SPLIT, ZMU>), dim3(grid), dim3(block), 0, st, ac);     \
-    else                                                                                                                                   \
+    if (integ == MF_INTEG_DYNAMICS) {                                                                                                      \
+      if constexpr (COST != 2) {                                                                                                           \
+        launched = true;                                                                                                                   \
+        MF_KLAUNCH((rollout_fwd_kernel<S, G_, P_, MF_INTEG_DYNAMICS, FAST, JOINTS, FORCES, COST, SPLIT, ZMU>), dim3(grid), dim3(block), 0, st, ac);   \
+      }                                                                                                                                    \
+    } else {                                                                                                                               \
+      launched = true;                                                                                                                     \
       MF_KLAUNCH((rollout_fwd_kernel<S, G_, P_, MF_INTEG_ODEINT_EULER, FAST, JOINTS, FORCES, COST, SPLIT, ZMU>), dim3(grid), dim3(block), 0, st, ac); \
+    }                                                                                                                                      \
   }
-  if (!JOINTS) { MF_CASE(4, 1) MF_CASE(8, 1) MF_CASE(16, 1) MF_CASE(32, 1) MF_CASE(64, 1) }
+  // (an articulated body: fwd_lane_map(d, true), rollout_route.hip, answers a multi-wave mapping or a 4-points-per-lane one, never these)
+  if constexpr (!JOINTS) { MF_CASE(4, 1) MF_CASE(8, 1) MF_CASE(16, 1) MF_CASE(32, 1) MF_CASE(64, 1) }
   if constexpr (!SPLIT && !ZMU) {   // SPLIT / ZMU kernels: the one-point-per-lane mappings up to a wave only
-  if (!JOINTS) { MF_CASE(64, 2) }
+  if constexpr (!JOINTS) { MF_CASE(64, 2) }
   MF_CASE(128, 1) MF_CASE(256, 1) MF_CASE(512, 1)
-  if (FORCES) { MF_CASE(1, 4) MF_CASE(2, 4) MF_CASE(4, 4) MF_CASE(8, 4) MF_CASE(16, 4) MF_CASE(32, 4) }
+  // (states only / cost rows: plan_fwd re-chooses (PPL = 4, G < 64) as one point per lane -- "r.m.PPL == 4 && r.m.G < 64", twice)
+  if constexpr (FORCES) { MF_CASE(1, 4) MF_CASE(2, 4) MF_CASE(4, 4) MF_CASE(8, 4) MF_CASE(16, 4) MF_CASE(32, 4) }
   MF_CASE(64, 4) MF_CASE(64, 8)
   }
 #undef MF_CASE

@@ -1,4 +1,4 @@
-"""Which kernel each rollout launch takes on the MI355X, pinned: one small launch (T = 3 on a 64^2 / 100^2 map) per branch of
+"""Which kernel each rollout launch takes on the MI355X, pinned: one small launch (T = 3 or 16 on a 64^2 / 100^2 map) per branch of
 mf_rollout_fwd_f32/f64 and mf_rollout_bwd_f32/f64 through the C ABI, and after each call the return code, mf_last_launch() -- the kernel
 template, grid and workgroup -- and how many rollout kernels the call launched; and the routes the Python wrappers pick from the policy
 queries (physics_loss_rollout by mf_rollout_loss_fusable's answer, rollout_costs).  The fixture, tests/golden/rollout_routes_gpu.json, was
@@ -61,6 +61,12 @@ CASES = {
     'xs_win_loss': dict(B=16384, shared=1, forces=False, up='loss'),
     'xs_ppl': dict(B=2048, N=223, up='xs'),
     'carry_ppl': dict(B=2048, N=223),
+    # the edges of the instantiated lane maps (tests/test_rollout_instances_cpu.py): an articulated body inside a wave and over four waves, a
+    # states-only launch that asks for four points per lane (the planner re-chooses one), projected cost rows under dynamics() (the COST = 1 kernel)
+    'joints_fast_ppl4_n4': dict(B=8, T=16, joints=1),
+    'joints_fast_multiwave': dict(B=4, T=16, N=223, joints=1),
+    'ppl4_states': dict(B=8, T=16, N=16, ppl=4, forces=False, up='xs'),
+    'cost2_dynamics': dict(B=8, T=16, cost=2, integ=0, up=None),
     # the float64 validation builds and the exact float64 kernels
     'f64_cp_stream': dict(f64=True, ppl=COMPONENT, B=64, rec=True),
     'f64_cp_saved': dict(f64=True, ppl=COMPONENT, B=64, rec=True, integ=0),
@@ -89,19 +95,20 @@ def _outcome(L, rc, n0):
     return [rc, name, grid, block, n - n0]
 
 
-def run_case(spec):
-    """[rc, kernel, grid, block, launches] of the forward and (unless up is None) the backward of one case."""
+def run_case(spec, rows=None):
+    """[rc, kernel, grid, block, launches] of the forward and (unless up is None) the backward of one case; `rows`: a list that receives
+    the forward's cost rows."""
     import torch
     from monoforce_amd import _lib
     L = _lib.lib()
     L.mf_rollout_record_bytes.restype = C.c_longlong
     L.mf_rollout_record_bytes_f64.restype = C.c_longlong
-    c = dict(B=64, N=4, side=64, integ=1, math=1, ppl=0, shared=0, joints=0, f64=False, forces=True, zmu_scratch=False, zmu=False,
+    c = dict(B=64, T=3, N=4, side=64, integ=1, math=1, ppl=0, shared=0, joints=0, f64=False, forces=True, zmu_scratch=False, zmu=False,
              rec=False, cost=0, loss=None, up='all', bwd_zmu_scratch=False, gcontrols=False)
     c.update(spec)
     dt = torch.float64 if c['f64'] else torch.float32
     sfx = 'f64' if c['f64'] else 'f32'
-    B, T, N, H = c['B'], 3, c['N'], c['side']
+    B, T, N, H = c['B'], c['T'], c['N'], c['side']      # (the loss tables below are those of T = 3)
     keep = []
 
     def put(t):
@@ -129,6 +136,7 @@ def run_case(spec):
                               R0=put(torch.eye(3, dtype=dt).repeat(B, 1, 1)), w0=buf(B * 3), Xs=buf(B * T * 3), Rs=buf(B * T * 9))
     if c['cost']:
         f.cost_rows, f.path_cost = buf(T * B * 4), buf(B)
+        cost_rows = keep[-2]
     else:
         f.Xds, f.Omegas, f.Xraw = buf(B * T * 3), buf(B * T * 3), buf(B * (T + 1) * 3)
         if c['forces']:
@@ -153,6 +161,8 @@ def run_case(spec):
     rc = getattr(L, 'mf_rollout_fwd_' + sfx)(C.byref(d), C.byref(f), None)
     out['fwd'] = _outcome(L, rc, n0)
     torch.cuda.synchronize()
+    if rows is not None:
+        rows.append(cost_rows.cpu())
     if c['up'] is None or rc != 0:
         return out
     g = _lib.MfRolloutBwdBufs(z=f.z, mu=f.mu, controls=f.controls, ts=f.ts, points=f.points, part=f.part, x_init=f.x0, xd0=f.xd0, R0=f.R0,
@@ -342,6 +352,17 @@ def test_fixture_covers_every_case():
 @pytest.mark.parametrize('name', sorted(CASES))
 def test_route_is_the_recorded_one(name):
     assert run_case(CASES[name]) == json.load(open(FIXTURE))[name]
+
+
+@pytest.mark.gpu
+def test_projected_cost_rows_under_dynamics_are_the_plain_ones():
+    """cost_project = 1 under dynamics(), whose rotation cannot drift, runs the COST = 1 kernel: the rows of cost_project = 0, bit for bit."""
+    import torch
+    rows = []
+    plain = run_case(dict(CASES['cost2_dynamics'], cost=1), rows)
+    assert run_case(CASES['cost2_dynamics'], rows) == plain
+    assert ', 0, true, false, false, 1, false, false, false>' in plain['fwd'][1]      # (INTEG = dynamics(), ..., COST = 1, ...)
+    assert rows[0].abs().max() > 0 and torch.equal(rows[0], rows[1])
 
 
 @pytest.mark.gpu
