@@ -425,6 +425,49 @@ int mf_pose_loss_bwd_f32(const MfPoseLossDesc* desc, const float* Xs, const floa
                          const int32_t* nearest, const float* gloss, float* gXs, float* gRs, void* hip_stream);
 int mf_pose_loss_bwd_f64(const MfPoseLossDesc* desc, const double* Xs, const double* Rs, const double* Xgt, const double* Rgt, const double* gt_ts,
                          const int32_t* nearest, const double* gloss, double* gXs, double* gRs, void* hip_stream);
+/* ---- height-map losses: hm_loss (losses.py:77-99) and total_variation (losses.py:68-74) ------------------------------------------------
+ * Maps are addressed as [M][H][W]: element (m, h, w) of a tensor sits at m*stride_m + h*stride_h + w (elements; unit stride along W), every
+ * tensor with its own pair of strides -- `hm_geom[:, 0:1]` / `hm_geom[:, 1:2]` of a [B,2,H,W] label tensor, `terrain['geom'][:, 0]`, a
+ * row-strided crop and a plain [H,W] map (M = 1) are read in place.  p_* address the prediction (total variation: the map z), g_* the
+ * label, w_* the weights, o_* the gradient a backward entry writes.  M * H * W must be below 2^31.  Every value entry finishes inside
+ * its launch like mf_pose_loss_value_*: `partial` holds ceil(M*H*W / 1024) scalars of scratch, `ticket` is ONE zero-initialised uint32
+ * the last workgroup resets (calls ordered on one stream may share it, also with mf_physics_loss_value_* / mf_pose_loss_value_*); the
+ * partial sums are added in block order: bit-identical from launch to launch.  No entry synchronises or allocates (capturable). */
+typedef struct MfMapLossDesc {
+  int32_t M, H, W;              /* maps, rows, columns */
+  int32_t use_h_max;            /* hm_loss: 1 = the prediction is h_max * tanh(pred) (losses.py:83-86), 0 = as it is (h_max=None) */
+  int64_t p_stride_m, p_stride_h;
+  int64_t g_stride_m, g_stride_h;
+  int64_t w_stride_m, w_stride_h;
+  int64_t o_stride_m, o_stride_h;
+  double h_max;
+} MfMapLossDesc;
+/* losses.py:77-99.  Per cell p' = use_h_max ? h_max * tanh(pred) : pred; the cell counts iff neither p' nor gt is NaN (:89);
+ *   loss[0] = sum_valid (p'*w - gt*w)^2 / n_valid (:95-97),   n_valid_out[0] = n_valid (an exact count, kept on the device for the backward)
+ * `w` may be NULL: all ones (:79-80).  `counts`: ceil(M*H*W / 1024) uint32 of scratch next to `partial`.  n_valid == 0 gives NaN, the
+ * reference's mean of an empty selection. */
+int mf_hm_loss_value_f32(const MfMapLossDesc* desc, const float* pred, const float* gt, const float* w, float* partial, uint32_t* counts,
+                         uint32_t* ticket, float* loss, int32_t* n_valid_out, void* hip_stream);
+int mf_hm_loss_value_f64(const MfMapLossDesc* desc, const double* pred, const double* gt, const double* w, double* partial, uint32_t* counts,
+                         uint32_t* ticket, double* loss, int32_t* n_valid_out, void* hip_stream);
+/* The autograd backward of losses.py:83-97 with respect to height_pred, given the upstream gradient gloss[0] and the count the value
+ * entry left in n_valid[0].  EVERY cell of g_pred (its own strides, o_*) is stored, not accumulated: it need not be zero on entry.
+ *   valid cells:  g_pred = gloss[0] * 2 w (p'*w - gt*w) / n_valid  [* h_max * (1 - tanh(pred)^2) under use_h_max];   masked cells: 0
+ * ONE difference from autograd: under use_h_max a NaN PREDICTION gets the reference's tanh backward 0 * (1 - NaN^2) = NaN at that cell;
+ * here it is 0.  Without use_h_max both give 0 there; with every cell masked both give all zeros. */
+int mf_hm_loss_bwd_f32(const MfMapLossDesc* desc, const float* pred, const float* gt, const float* w, const int32_t* n_valid,
+                       const float* gloss, float* g_pred, void* hip_stream);
+int mf_hm_loss_bwd_f64(const MfMapLossDesc* desc, const double* pred, const double* gt, const double* w, const int32_t* n_valid,
+                       const double* gloss, double* g_pred, void* hip_stream);
+/* losses.py:68-74: loss[0] = (sum |z[m,h,w+1] - z[m,h,w]| + sum |z[m,h+1,w] - z[m,h,w]|) / (H * W).  The differences stay inside each of
+ * the M maps and the divisor is H * W whatever M is (:69, :73); H == 1 or W == 1 has no differences along that axis.  Strides: p_*. */
+int mf_total_variation_value_f32(const MfMapLossDesc* desc, const float* z, float* partial, uint32_t* ticket, float* loss, void* hip_stream);
+int mf_total_variation_value_f64(const MfMapLossDesc* desc, const double* z, double* partial, uint32_t* ticket, double* loss, void* hip_stream);
+/* The autograd backward of losses.py:71-73: every cell of g_z (strides o_*) is STORED with gloss[0] / (H * W) times the signed sum of its up
+ * to four neighbour terms, sgn(z - left) - sgn(right - z) + sgn(z - up) - sgn(down - z); sgn(0) = 0 as torch's abs backward has it (a flat
+ * map has an exactly zero gradient).  A gather per cell: no atomics. */
+int mf_total_variation_bwd_f32(const MfMapLossDesc* desc, const float* z, const float* gloss, float* g_z, void* hip_stream);
+int mf_total_variation_bwd_f64(const MfMapLossDesc* desc, const double* z, const double* gloss, double* g_z, void* hip_stream);
 /* The reduction that follows a shared-map mf_rollout_bwd_* (MfRolloutDesc.grad_copies private copies of each map gradient,
  * pool = [n_maps][copies][n]):  out[m][i] = sum_c pool[m][c][i], and pool is left ZEROED -- a caller that keeps the pool across
  * steps never fills it again (replaces a zero fill + `maps.sum(1)`, scripts/train.py's optimizer step reads `out`). */

@@ -71,5 +71,6 @@ extern "C" int mf_sizeof(const char* name) {
   if (!strcmp(name, "MfMppiDesc")) return (int)sizeof(MfMppiDesc);
   if (!strcmp(name, "MfPoseCostDesc")) return (int)sizeof(MfPoseCostDesc);
   if (!strcmp(name, "MfPoseLossDesc")) return (int)sizeof(MfPoseLossDesc);
+  if (!strcmp(name, "MfMapLossDesc")) return (int)sizeof(MfMapLossDesc);
   return -1;
 }

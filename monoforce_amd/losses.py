@@ -5,7 +5,8 @@ tensors are on).  Semantics of `/root/reference/monoforce/src/monoforce/losses.p
 The loss kernels of the C ABI (`mf_physics_loss_*`, `mf_pose_loss_*`, `mf_nearest_steps_*`) are marshalled here and nowhere else: one
 function per entry point (`loss_value`, `loss_backward`, `pose_loss_value`, `pose_loss_backward`, `nearest_steps_hip`) builds the
 descriptor, sizes the partial sums and launches through `_lib.launch`; the autograd functions below and the rollout's fused-loss route
-(dphysics.py) call them.
+(dphysics.py) call them.  Likewise the two losses on a terrain map, `mf_hm_loss_*` and `mf_total_variation_*` (`hm_loss_value`,
+`hm_loss_backward`, `total_variation_value`, `total_variation_backward`).
 """
 import ctypes as C
 
@@ -14,13 +15,29 @@ import torch
 from . import _lib
 
 _HIP_LOSS = True      # physics_loss on GPU tensors runs on the mf_physics_loss_* kernels (False: the reference's ATen form)
+_HIP_MAP_LOSS = True  # hm_loss / total_variation on GPU tensors run on the mf_hm_loss_* / mf_total_variation_* kernels (False: the ATen forms)
 
-__all__ = ['nearest_steps', 'nearest_steps_hip', 'physics_loss', 'physics_loss_aten', 'physics_loss_fused', 'hm_loss', 'total_variation', 'rotation_difference',
-           'translation_difference', 'slerp']
+__all__ = ['nearest_steps', 'nearest_steps_hip', 'physics_loss', 'physics_loss_aten', 'physics_loss_fused', 'hm_loss', 'hm_loss_aten',
+           'total_variation', 'total_variation_aten', 'rotation_difference', 'translation_difference', 'slerp']
+
+
+def _map_dtype_ok(t):
+    return t.is_cuda and t.dtype in (torch.float32, torch.float64) and t.dim() >= 2 and 0 < t.numel() < 2 ** 31
 
 
 def total_variation(heightmap):
-    """(sum |d/dy| + sum |d/dx|) / (h w) (losses.py:68-74)."""
+    """(sum |d/dy| + sum |d/dx|) / (h w) (losses.py:68-74) of a map [...,h,w]; the differences stay inside each map, the divisor is h w
+    however many maps there are.  A float32 / float64 map on the MI355X: one `mf_total_variation_value_*` launch, and one
+    `mf_total_variation_bwd_*` launch for the gradient (`_FusedTotalVariation`), instead of the eleven ATen launches of
+    `total_variation_aten` and as many again backward; channel views, row-strided crops and [h,w] maps are read in place.  `sign(0) = 0`
+    as in torch's `abs` backward.  `monoforce_amd.losses._HIP_MAP_LOSS = False` keeps the ATen form everywhere."""
+    if _HIP_MAP_LOSS and _map_dtype_ok(heightmap):
+        return _FusedTotalVariation.apply(heightmap)
+    return total_variation_aten(heightmap)
+
+
+def total_variation_aten(heightmap):
+    """The reference's formulation (losses.py:68-74) in plain torch ops, on whatever device the tensor is on."""
     h, w = heightmap.shape[-2:]
     dv = (heightmap[..., :, 1:] - heightmap[..., :, :-1]).abs().sum()
     dh = (heightmap[..., 1:, :] - heightmap[..., :-1, :]).abs().sum()
@@ -28,7 +45,34 @@ def total_variation(heightmap):
 
 
 def hm_loss(height_pred, height_gt, weights=None, h_max=None):
-    """Weighted MSE between height maps over the cells where both are finite (losses.py:77-99)."""
+    """Weighted MSE between height maps over the cells where both are finite (losses.py:77-99).
+    Tensors on the MI355X: one `mf_hm_loss_value_*` launch (the masked sum, the count of valid cells and their quotient) and one
+    `mf_hm_loss_bwd_*` launch for the gradient (`_FusedHmLoss`) instead of about a dozen ATen launches each way -- where that IS the
+    reference's result: float32 / float64 tensors of one dtype on one device, labels and weights that do not require grad, `h_max` a
+    number.  Channel views of a [B,2,H,W] label tensor (`hm_geom[:, 0:1]`, `hm_geom[:, 1]`), row-strided crops and [H,W] maps are read in
+    place; any other layout through one `.contiguous()`.  One documented difference from autograd: with `h_max` set, a NaN PREDICTION
+    gets a NaN gradient at that cell from torch's tanh backward (0 * (1 - NaN^2)); the kernel's gradient is 0 there, like at every other
+    masked cell.  Everything else takes `hm_loss_aten`.  `monoforce_amd.losses._HIP_MAP_LOSS = False` keeps the ATen form everywhere."""
+    assert height_pred.shape == height_gt.shape, 'Height prediction and ground truth must have the same shape'
+    assert weights is None or weights.shape == height_gt.shape, 'Weights and height ground truth must have the same shape'
+    if _HIP_MAP_LOSS and _hm_loss_takes_the_hip_route(height_pred, height_gt, weights, h_max):
+        return _FusedHmLoss.apply(height_pred, height_gt, weights, h_max)
+    return hm_loss_aten(height_pred, height_gt, weights=weights, h_max=h_max)
+
+
+def _hm_loss_takes_the_hip_route(height_pred, height_gt, weights, h_max):
+    """`hm_loss`'s route decision (the kernels return the loss in the prediction's dtype and send no gradient to labels or weights)."""
+    if not (_map_dtype_ok(height_pred) and (h_max is None or isinstance(h_max, (int, float)))):
+        return False
+    for t in (height_gt,) if weights is None else (height_gt, weights):
+        if not (torch.is_tensor(t) and t.device == height_pred.device and t.dtype == height_pred.dtype and not t.requires_grad):
+            return False
+    return True
+
+
+def hm_loss_aten(height_pred, height_gt, weights=None, h_max=None):
+    """The reference's formulation (losses.py:77-99) in plain torch ops, on whatever device the tensors are on -- what `hm_loss` runs on CPU
+    tensors and for everything its HIP route declines."""
     assert height_pred.shape == height_gt.shape, 'Height prediction and ground truth must have the same shape'
     if weights is None:
         weights = torch.ones_like(height_gt)
@@ -269,6 +313,170 @@ def pose_loss_backward(desc, X_pred, R_pred, X_gt, R_gt, gt_ts, near, gl, gX, gR
     """One `mf_pose_loss_bwd_*` launch: gl [2] = the two upstream gradients; `gX` / `gR` zeroed, None = that half is not formed."""
     _lib.launch('mf_pose_loss_bwd', X_pred.device, desc, X_pred, R_pred, X_gt, R_gt, gt_ts, near, gl, gX, gR, dtype=X_pred.dtype,
                 timer='pose_loss_bwd')
+
+
+_MAP_CHUNK = 1024     # cells per workgroup of the map-loss kernels (map_losses.hip): one partial sum each
+
+
+def map_strides(t):
+    """A map tensor [...,H,W] as the map-loss kernels address it, [M][H][W] with unit stride along W: (tensor, stride_m, stride_h) in
+    elements.  The leading axes must fold into ONE axis with one stride (axes of size 1 do not count): channel views of a [B,2,H,W]
+    tensor, row-strided crops and [H,W] maps come back as they are, everything else (a strided W, leading axes that do not fold) as
+    one `.contiguous()` copy."""
+    for _ in range(2):
+        lead = [(n, s) for n, s in zip(t.shape[:-2], t.stride()[:-2]) if n != 1]
+        if (t.shape[-1] == 1 or t.stride(-1) == 1) and all(s0 == s1 * n1 for (_n0, s0), (n1, s1) in zip(lead, lead[1:])):
+            return t, (lead[-1][1] if lead else 0), t.stride(-2)
+        t = t.contiguous()
+    raise AssertionError('a contiguous tensor folds')
+
+
+def _map_desc(shape, **kw):
+    H, W = shape[-2:]
+    n = 1
+    for v in shape:
+        n *= v
+    return _lib.MfMapLossDesc(M=n // (H * W), H=H, W=W, **kw), (n + _MAP_CHUNK - 1) // _MAP_CHUNK
+
+
+def _grad_strides(g, like):
+    """(stride_m, stride_h) of a gradient buffer the backward kernels store into: the shape, dtype and device of the tensor they read, and a
+    layout they address without a copy (a copy would receive the stores instead of the buffer)."""
+    assert g.shape == like.shape and g.dtype == like.dtype and g.device == like.device, 'the gradient buffer must match the map tensor'
+    view, sm, sh = map_strides(g)
+    assert view is g, f'a gradient buffer of strides {g.stride()} is not addressable as [M][H][W] with unit stride along W'
+    return sm, sh
+
+
+def hm_loss_state(pred, gt, weights, h_max):
+    """What both `mf_hm_loss_*` launches take: (descriptor, pred, gt, weights) -- map tensors of one shape [...,H,W] and one dtype
+    (weights None: all ones) as the kernels read them, each in place where `map_strides` returns it unchanged."""
+    (pred, psm, psh), (gt, gsm, gsh) = map_strides(pred), map_strides(gt)
+    weights, wsm, wsh = (None, 0, 0) if weights is None else map_strides(weights)
+    desc, _ = _map_desc(pred.shape, use_h_max=int(h_max is not None), h_max=0.0 if h_max is None else float(h_max), p_stride_m=psm,
+                        p_stride_h=psh, g_stride_m=gsm, g_stride_h=gsh, w_stride_m=wsm, w_stride_h=wsh)
+    return desc, pred, gt, weights
+
+
+def hm_loss_value(pred, gt, weights, h_max, ticket, loss, n_valid):
+    """One `mf_hm_loss_value_*` launch: `loss` (a scalar tensor) <- hm_loss of pred against gt and weights; `n_valid` (int32 [1]) <- the
+    number of cells that count; `ticket`: `_ticket`'s counter of the current stream.  Returns `hm_loss_state`, which the backward takes."""
+    desc, pred, gt, weights = state = hm_loss_state(pred, gt, weights, h_max)
+    blocks = _map_desc(pred.shape)[1]
+    partial = torch.empty(blocks, dtype=pred.dtype, device=pred.device)
+    counts = torch.empty(blocks, dtype=torch.int32, device=pred.device)
+    _lib.launch('mf_hm_loss_value', pred.device, desc, pred, gt, weights, partial, counts, ticket, loss, n_valid, dtype=pred.dtype,
+                timer='hm_loss_fwd')
+    return state
+
+
+def hm_loss_backward(desc, pred, gt, weights, n_valid, gloss, g_pred):
+    """One `mf_hm_loss_bwd_*` launch: every cell of `g_pred` (pred's shape, its own strides, in a layout `map_strides` returns unchanged;
+    no need to clear it) <- gloss [1] x d loss / d pred; (desc, pred, gt, weights) as `hm_loss_value` returned them."""
+    desc.o_stride_m, desc.o_stride_h = _grad_strides(g_pred, pred)
+    _lib.launch('mf_hm_loss_bwd', pred.device, desc, pred, gt, weights, n_valid, gloss, g_pred, dtype=pred.dtype, timer='hm_loss_bwd')
+
+
+def total_variation_state(z):
+    """What both `mf_total_variation_*` launches take: (descriptor, z as the kernels read it -- in place, or its contiguous copy)."""
+    z, sm, sh = map_strides(z)
+    return _map_desc(z.shape, p_stride_m=sm, p_stride_h=sh)[0], z
+
+
+def total_variation_value(z, ticket, loss):
+    """One `mf_total_variation_value_*` launch: `loss` (a scalar tensor) <- total_variation of the map tensor z [...,H,W].  Returns
+    `total_variation_state`, which the backward takes."""
+    desc, z = state = total_variation_state(z)
+    partial = torch.empty(_map_desc(z.shape)[1], dtype=z.dtype, device=z.device)
+    _lib.launch('mf_total_variation_value', z.device, desc, z, partial, ticket, loss, dtype=z.dtype, timer='total_variation_fwd')
+    return state
+
+
+def total_variation_backward(desc, z, gloss, g_z):
+    """One `mf_total_variation_bwd_*` launch: every cell of `g_z` (z's shape, its own strides, no need to clear it) <- gloss [1] x d loss / d z."""
+    desc.o_stride_m, desc.o_stride_h = _grad_strides(g_z, z)
+    _lib.launch('mf_total_variation_bwd', z.device, desc, z, gloss, g_z, dtype=z.dtype, timer='total_variation_bwd')
+
+
+def hm_loss_forward(height_pred, height_gt, weights=None, h_max=None):
+    """`hm_loss` on the HIP kernels without autograd: (loss, n_valid, state); `n_valid` is the int32 [1] device count of the cells that
+    entered the mean, `state` what `hm_loss_grad` takes."""
+    _lib.require_hip_tensor(height_pred, 'height_pred')
+    _register_reset()
+    dev, dt = height_pred.device, height_pred.dtype
+    loss = torch.empty((), dtype=dt, device=dev)
+    n_valid = torch.empty(1, dtype=torch.int32, device=dev)
+    state = hm_loss_value(height_pred.detach(), height_gt.detach().to(dt), None if weights is None else weights.detach().to(dt), h_max,
+                          _ticket(dev, torch.cuda.current_stream(dev)), loss, n_valid)
+    return loss, n_valid, state
+
+
+def hm_loss_grad(state, n_valid, gloss, shape):
+    """d hm_loss / d height_pred x gloss (a device scalar), a fresh contiguous tensor of `shape`: one launch, every cell stored."""
+    desc, pred, gt, weights = state
+    g_pred = torch.empty(shape, dtype=pred.dtype, device=pred.device)
+    hm_loss_backward(desc, pred, gt, weights, n_valid, gloss.detach().to(pred.dtype).reshape(1), g_pred)
+    return g_pred
+
+
+class _FusedHmLoss(torch.autograd.Function):
+    """`mf_hm_loss_value/bwd_*`: `hm_loss` as one masked-reduce kernel forward (sum, count and quotient) and one kernel backward that stores
+    every cell; the count stays on the device between the two.  A NaN prediction under `h_max` has gradient 0 (torch's tanh backward: NaN),
+    see `hm_loss`."""
+
+    @staticmethod
+    def forward(ctx, height_pred, height_gt, weights, h_max):
+        loss, n_valid, (desc, pred, gt, w) = hm_loss_forward(height_pred, height_gt, weights, h_max)
+        if ctx.needs_input_grad[0]:
+            ctx.desc, ctx.has_w, ctx.shape = desc, w is not None, height_pred.shape
+            ctx.save_for_backward(pred, gt, n_valid, *(() if w is None else (w,)))
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        if gloss is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        pred, gt, n_valid = ctx.saved_tensors[:3]
+        w = ctx.saved_tensors[3] if ctx.has_w else None
+        return hm_loss_grad((ctx.desc, pred, gt, w), n_valid, gloss, ctx.shape), None, None, None
+
+
+def total_variation_forward(heightmap):
+    """`total_variation` on the HIP kernels without autograd: (loss, state); `state` is what `total_variation_grad` takes."""
+    _lib.require_hip_tensor(heightmap, 'heightmap')
+    _register_reset()
+    dev = heightmap.device
+    loss = torch.empty((), dtype=heightmap.dtype, device=dev)
+    return loss, total_variation_value(heightmap.detach(), _ticket(dev, torch.cuda.current_stream(dev)), loss)
+
+
+def total_variation_grad(state, gloss, shape):
+    """d total_variation / d heightmap x gloss (a device scalar), a fresh contiguous tensor of `shape`: one launch, every cell stored."""
+    desc, z = state
+    g_z = torch.empty(shape, dtype=z.dtype, device=z.device)
+    total_variation_backward(desc, z, gloss.detach().to(z.dtype).reshape(1), g_z)
+    return g_z
+
+
+class _FusedTotalVariation(torch.autograd.Function):
+    """`mf_total_variation_value/bwd_*`: one reduce kernel forward, one gather kernel backward (the signed sum of a cell's up to four
+    neighbour terms, sign(0) = 0; no atomics)."""
+
+    @staticmethod
+    def forward(ctx, heightmap):
+        loss, (desc, z) = total_variation_forward(heightmap)
+        if ctx.needs_input_grad[0]:
+            ctx.desc, ctx.shape = desc, heightmap.shape
+            ctx.save_for_backward(z)
+        ctx.set_materialize_grads(False)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        if gloss is None or not ctx.needs_input_grad[0]:
+            return None
+        return total_variation_grad((ctx.desc, ctx.saved_tensors[0]), gloss, ctx.shape)
 
 
 class _FusedPhysicsLoss(torch.autograd.Function):

@@ -20,6 +20,8 @@ Schemas (tensors on the GPU, float32 or float64; `Bz` in {1, B}: a [1,H,W] map i
                                  -> (Tensor nominal, Tensor weights, Tensor best, Tensor n_valid)
     monoforce::pose_costs(Tensor Xs, Tensor Rs, Tensor points, Tensor? cost_map, Tensor? path, Tensor? base_costs, float grid_res,
                           float d_max, float lethal, float off_map, float[] weights) -> (Tensor costs, Tensor terms)
+    monoforce::hm_loss(Tensor height_pred, Tensor height_gt, Tensor? weights, float? h_max) -> (Tensor loss, Tensor n_valid)
+    monoforce::total_variation(Tensor heightmap) -> Tensor loss
 
 `consts` = [mass, gravity, stiffness, damping, grid_res, d_max, dt, omega_max, robot_size_y(, traj_sim_time)]; `part_id[N]` int32
 (index of the last driving mask holding the point, -1 = not driving); `Iinv` [3,3] on the HOST (nine scalars of the launch
@@ -41,6 +43,11 @@ are int32 [1] on the device.
 `points` [N,3] the footprint in the body frame; `cost_map` [H,W] on the nodes of z_grid; `path` [P,2]; `weights` = (map, path), each 0 when
 its input is None; `costs` [B] = base_costs + w_map map + w_path xtrack, `terms` [B,2] = (map, xtrack).  One launch.
 
+`hm_loss` / `total_variation` (float32 or float64, autograd to `height_pred` / `heightmap`; monoforce_amd/csrc/map_losses.hip, formulas in
+include/monoforce_hip.h at MfMapLossDesc): map tensors [...,H,W], channel views and row-strided crops read in place; `loss` a scalar, `n_valid`
+int32 [1] = the cells that entered the mean.  One launch forward, one backward; both delegate to monoforce_amd/losses.py, which marshals
+the entry points (its `hm_loss` / `total_variation` are the drop-in forms, with the ATen route for CPU tensors).
+
 The rollout ops and `DPhysics`'s own autograd function (monoforce_amd/dphysics.py: more options -- articulated bodies, path costs,
 strided controls) launch through the same marshalling (monoforce_amd/rollout_launch.py), the splat ops and `voxel_pooling` likewise
 (monoforce_amd/splat.py); only the MPPI and pose-cost entry points, which have no other caller, are marshalled here (`_lib.launch`).
@@ -50,7 +57,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib, rollout_launch as rl, splat as _splat
+from . import _lib, losses as _losses, rollout_launch as rl, splat as _splat
 
 
 class _PoolOwner:       # the registered ops have no module to hang the persistent gradient-copy pools on
@@ -77,6 +84,8 @@ _L.define('path_costs(Tensor cost_rows, Tensor? force_cost, Tensor x_last, Tenso
 _L.define('mppi_update(Tensor costs, Tensor controls, Tensor nominal, float lam) -> (Tensor, Tensor, Tensor, Tensor)')
 _L.define('pose_costs(Tensor Xs, Tensor Rs, Tensor points, Tensor? cost_map, Tensor? path, Tensor? base_costs, float grid_res, float d_max, '
           'float lethal, float off_map, float[] weights) -> (Tensor, Tensor)')
+_L.define('hm_loss(Tensor height_pred, Tensor height_gt, Tensor? weights, float? h_max) -> (Tensor, Tensor)')
+_L.define('total_variation(Tensor heightmap) -> Tensor')
 
 
 def _time_grid(consts, T, dt, dev):
@@ -359,6 +368,71 @@ def _pose_costs(Xs, Rs, points, cost_map, path, base_costs, grid_res, d_max, let
 def _pose_costs_fake(Xs, Rs, points, cost_map, path, base_costs, grid_res, d_max, lethal, off_map, weights):
     B = Xs.shape[0]
     return Xs.new_empty(B), Xs.new_empty(B, 2)
+
+
+# ---- height-map losses ---------------------------------------------------------------------------------------------------------------
+def _map_loss_input(ok, what):
+    if not ok:
+        raise TypeError(f'monoforce::{what}: float32 / float64 map tensors [...,H,W] of one dtype on one GPU, below 2^31 cells, are expected '
+                        '(monoforce_amd.losses has the ATen forms for everything else)')
+
+
+@torch.library.impl(_L, 'hm_loss', 'CUDA')
+def _hm_loss(height_pred, height_gt, weights, h_max):
+    _map_loss_input(height_pred.shape == height_gt.shape and (weights is None or weights.shape == height_gt.shape)
+                    and _losses._hm_loss_takes_the_hip_route(height_pred, height_gt.detach(), None if weights is None else weights.detach(), h_max),
+                    'hm_loss')
+    loss, n_valid, _ = _losses.hm_loss_forward(height_pred, height_gt, weights, h_max)
+    return loss, n_valid
+
+
+def _hm_loss_setup(ctx, inputs, output):
+    height_pred, height_gt, weights, h_max = inputs
+    ctx.h_max, ctx.has_w = h_max, weights is not None
+    ctx.save_for_backward(height_pred, height_gt, output[1], *(() if weights is None else (weights,)))
+    ctx.set_materialize_grads(False)
+
+
+def _hm_loss_backward(ctx, gloss, _g_n_valid):
+    if gloss is None or not ctx.needs_input_grad[0]:
+        return None, None, None, None
+    pred, gt, n_valid = ctx.saved_tensors[:3]
+    state = _losses.hm_loss_state(pred.detach(), gt.detach(), ctx.saved_tensors[3].detach() if ctx.has_w else None, ctx.h_max)
+    return _losses.hm_loss_grad(state, n_valid, gloss, pred.shape), None, None, None
+
+
+torch.library.register_autograd('monoforce::hm_loss', _hm_loss_backward, setup_context=_hm_loss_setup, lib=_L)
+
+
+@torch.library.register_fake('monoforce::hm_loss', lib=_L)
+def _hm_loss_fake(height_pred, height_gt, weights, h_max):
+    return height_pred.new_empty(()), height_pred.new_empty(1, dtype=torch.int32)
+
+
+@torch.library.impl(_L, 'total_variation', 'CUDA')
+def _total_variation(heightmap):
+    _map_loss_input(_losses._map_dtype_ok(heightmap), 'total_variation')
+    return _losses.total_variation_forward(heightmap)[0]
+
+
+def _total_variation_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0])
+    ctx.set_materialize_grads(False)
+
+
+def _total_variation_backward(ctx, gloss):
+    if gloss is None:
+        return None
+    z, = ctx.saved_tensors
+    return _losses.total_variation_grad(_losses.total_variation_state(z.detach()), gloss, z.shape)
+
+
+torch.library.register_autograd('monoforce::total_variation', _total_variation_backward, setup_context=_total_variation_setup, lib=_L)
+
+
+@torch.library.register_fake('monoforce::total_variation', lib=_L)
+def _total_variation_fake(heightmap):
+    return heightmap.new_empty(())
 
 
 # ---- functional entries ------------------------------------------------------------------------------------------------------

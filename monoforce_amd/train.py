@@ -7,7 +7,7 @@ import torch
 
 from . import dist as mfdist
 from .capture import capture
-from .losses import nearest_steps, physics_loss, physics_loss_fused
+from .losses import nearest_steps, physics_loss, physics_loss_fused, total_variation
 
 
 class TerrainFitProblem:
@@ -17,8 +17,11 @@ class TerrainFitProblem:
     The ground truth is a rollout of the same controls on a "true" terrain, generated once with the HIP forward.
     """
 
-    def __init__(self, dphysics, z_true, mu_true, controls, gt_every=10, fused_loss=True, graph=False, loss_in_kernel=True):
+    def __init__(self, dphysics, z_true, mu_true, controls, gt_every=10, fused_loss=True, graph=False, loss_in_kernel=True, tv_weight=0.0):
         self.dp = dphysics
+        # the regulariser of scripts/fit_terrain.py:58: loss = physics + tv_weight * total_variation(z), two more kernel launches per step
+        # (mf_total_variation_*); 0.0: the physics loss alone, launch for launch the step without this argument
+        self.tv_weight = float(tv_weight)
         self.fused_loss = fused_loss      # mf_physics_loss_* instead of ~25 small ATen kernels (same value and gradient)
         # physics_loss inside the rollout's own two launches (DPhysics.physics_loss_rollout; SURVEY 8f rank 1): a step is four
         # launches instead of six and the [B,T,3] gradient rows are never built; where the library cannot fuse, the route above
@@ -82,10 +85,16 @@ class TerrainFitProblem:
         return self._exchange(z, mu, loss)
 
     def _loss(self, z, mu):
+        if self.tv_weight == 0.0:
+            return self._physics(z, mu)
+        # (the sum is formed in the forward: the physics value must exist there, not only after the backward launch)
+        return self._physics(z, mu, value_in_backward=False) + self.tv_weight * total_variation(z)
+
+    def _physics(self, z, mu, value_in_backward=True):
         if self.loss_in_kernel:
             # (the step always runs the backward next and hands the value out afterwards: the backward launch forms it too)
             return self.dp.physics_loss_rollout(z.unsqueeze(0), self.controls, self.states_gt[0], self.spec, friction=mu.unsqueeze(0),
-                                                value_in_backward=self.loss_value_in_backward)[0]
+                                                value_in_backward=value_in_backward and self.loss_value_in_backward)[0]
         # (the fit discards the forces, scripts/fit_terrain.py:56: the forward writes the states only -- for the reference's 223-point
         #  body that is 36 of 241 MB per launch)
         states, _ = self.dp(z.unsqueeze(0), self.controls, friction=mu.unsqueeze(0), _want_forces=False)
