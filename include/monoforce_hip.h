@@ -468,6 +468,44 @@ int mf_total_variation_value_f64(const MfMapLossDesc* desc, const double* z, dou
  * map has an exactly zero gradient).  A gather per cell: no atomics. */
 int mf_total_variation_bwd_f32(const MfMapLossDesc* desc, const float* z, const float* gloss, float* g_z, void* hip_stream);
 int mf_total_variation_bwd_f64(const MfMapLossDesc* desc, const double* z, const double* gloss, double* g_z, void* hip_stream);
+/* ---- the optimisation loop of scripts/fit_terrain.py:46-69 around a fit step: Adam on both maps + best-so-far, ONE launch ---------------
+ * Everything the loop keeps between iterations lives on the device, so an iteration needs no host read (no `loss.item()`) and the launch
+ * can sit behind the step's launches in one hipGraph.  For both maps (n_z height cells, n_mu friction cells; the counts may differ, n_mu
+ * may be 0 with NULL friction pointers) and t = state[0] + 1, torch.optim.Adam's default single-tensor step (fit_terrain.py:46-49, :62;
+ * amsgrad=False, weight_decay=0, maximize=False), in ATen's order of operations and rounded op by op:
+ *   m = b1 m + (1 - b1) g  (as lerp(m, g, 1 - b1));   v = b2 v + (1 - b2) g g;   bc1 = 1 - b1^t,  bc2 = 1 - b2^t  (double, on the device)
+ *   p = p + (-(lr / bc1) m) / (sqrt(v) / sqrt(bc2) + eps),   lr per map;   a cell whose g, m, v are 0 keeps its bits
+ *   then, per map and only under its flag, the box projection p = min(max(p, lo), hi) (no reference equivalent; a NaN stays a NaN).  The
+ *   moments never see the projection.
+ * Best-so-far as fit_terrain.py:61-69 has it: loss[0] is the loss at the parameters BEFORE this update; improved = loss[0] < loss_min[0]
+ * (strict: a tie or a NaN is no improvement); when improved, z_best / mu_best take the parameters AFTER this update (the reference clones
+ * z_grid behind optimizer.step(); mu_best is an extension), loss_min[0] = loss[0], state[1] = state[0].
+ *   state[4] int32 = (step, best_step, ticket, reserved), at reset (0, -1, 0, 0);  loss_min[0] = +inf at reset
+ *   history[max_iters]: history[step] = loss[0] while step < max_iters; beyond that the write is dropped and step keeps counting
+ * Every workgroup reads step, loss and loss_min before its cells; behind them it fences and takes a ticket, and the workgroup that draws
+ * the last one commits the four scalars and resets the ticket (mf_pose_loss_value_*'s finish): no workgroup of the launch can see the
+ * next iteration's scalars.  Calls that share a state must be ordered on one stream.  Contiguous buffers; g_*, loss are read only; no
+ * entry synchronises or allocates (capturable).  The grid is min(mf_terrain_fit_grid_cap(), ceil((n_z + n_mu) / 256)) workgroups of 256
+ * threads in a grid-stride loop. */
+#define MF_FIT_CLAMP_Z 1
+#define MF_FIT_CLAMP_MU 2
+typedef struct MfFitDesc {
+  int64_t n_z, n_mu;            /* cells of the height map (> 0) and of the friction map (>= 0) */
+  int32_t max_iters;            /* length of `history` (>= 0; 0: history may be NULL) */
+  int32_t flags;                /* MF_FIT_CLAMP_*: which map is projected into its box */
+  double lr_z, lr_mu;           /* >= 0 */
+  double beta1, beta2;          /* in [0, 1) */
+  double eps;                   /* > 0 */
+  double z_lo, z_hi, mu_lo, mu_hi; /* read under the map's flag only; lo <= hi */
+} MfFitDesc;
+int mf_terrain_fit_update_f32(const MfFitDesc* desc, float* z, float* mu, const float* g_z, const float* g_mu, float* m_z, float* v_z,
+                              float* m_mu, float* v_mu, const float* loss, float* z_best, float* mu_best, int32_t* state, float* loss_min,
+                              float* history, void* hip_stream);
+int mf_terrain_fit_update_f64(const MfFitDesc* desc, double* z, double* mu, const double* g_z, const double* g_mu, double* m_z, double* v_z,
+                              double* m_mu, double* v_mu, const double* loss, double* z_best, double* mu_best, int32_t* state,
+                              double* loss_min, double* history, void* hip_stream);
+/* The most workgroups an mf_terrain_fit_update_* launch uses (more than cap x 256 cells: further trips of the grid-stride loop). */
+int mf_terrain_fit_grid_cap(void);
 /* The reduction that follows a shared-map mf_rollout_bwd_* (MfRolloutDesc.grad_copies private copies of each map gradient,
  * pool = [n_maps][copies][n]):  out[m][i] = sum_c pool[m][c][i], and pool is left ZEROED -- a caller that keeps the pool across
  * steps never fills it again (replaces a zero fill + `maps.sum(1)`, scripts/train.py's optimizer step reads `out`). */

@@ -23,4 +23,7 @@ def __getattr__(name):
     if name == 'MPPIPlanner':
         from .mppi import MPPIPlanner
         return MPPIPlanner
+    if name == 'TerrainFitter':
+        from .fit import TerrainFitter
+        return TerrainFitter
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -72,5 +72,6 @@ extern "C" int mf_sizeof(const char* name) {
   if (!strcmp(name, "MfPoseCostDesc")) return (int)sizeof(MfPoseCostDesc);
   if (!strcmp(name, "MfPoseLossDesc")) return (int)sizeof(MfPoseLossDesc);
   if (!strcmp(name, "MfMapLossDesc")) return (int)sizeof(MfMapLossDesc);
+  if (!strcmp(name, "MfFitDesc")) return (int)sizeof(MfFitDesc);
   return -1;
 }

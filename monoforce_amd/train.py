@@ -116,13 +116,18 @@ class TerrainFitProblem:
         z.grad, mu.grad = cap['gz'], cap['gmu']
         return self._exchange(z, mu, cap['loss'])
 
+    def _fwd_bwd(self, z, mu):
+        """Forward, loss and backward as the captured step runs them (no `.grad`, no exchange): (loss, d loss / d z, d loss / d mu).  Also
+        what `fit.TerrainFitter` captures in front of its update launch."""
+        loss = self._loss(z, mu)
+        gz, gmu = torch.autograd.grad(loss, [z, mu], grad_outputs=self._seed(loss))
+        return loss.detach(), gz, gmu
+
     def _capture(self, z, mu):
         dev = z.device
 
         def fwd_bwd():
-            loss = self._loss(z, mu)
-            gz, gmu = torch.autograd.grad(loss, [z, mu], grad_outputs=self._seed(loss))
-            return loss.detach(), gz, gmu
+            return self._fwd_bwd(z, mu)
 
         s = torch.cuda.Stream(device=dev)
         s.wait_stream(torch.cuda.current_stream(dev))
