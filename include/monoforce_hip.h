@@ -630,6 +630,72 @@ int mf_pose_costs_f32(const MfPoseCostDesc* desc, const float* Xs, const float* 
                       const float* cost_map /* [H][W] or NULL */, const float* path /* [P][2] or NULL iff P == 0 */,
                       const float* base_costs /* [B] or NULL */, float* costs /* [B] */, float* terms /* [B][2] or NULL */, void* hip_stream);
 
+/* ---- Planner cost WITH its gradient, from the full outputs of the differentiable rollout (no reference equivalent) ------------------------
+ * What an MPPI step scores (mf_pose_costs_f32 + mf_path_costs_f32 without the force term), as one differentiable objective, value and
+ * gradient in ONE launch.  Xs [B][T][3] (the sink-shifted positions DPhysics.forward returns) and Rs [B][T][3][3] are read in place through
+ * the strides.  Kept steps, by the rule of DPhysics.rollout_costs: t_p = min(p * pose_stride, T - 1) for p < Tp = 1 + ceil((T-1) / pose_stride).
+ *   J[b] = w_map  (1/Tp) sum_p max_n s(b,p,n)  +  w_path (1/Tp) sum_p d(b,p)  +  w_goal |Xs[b,T-1,0:2] - goal|
+ *        + w_incl (1/Tp) sum_p (|roll| + |pitch|)
+ * s and d are the footprint sample and the polyline distance of mf_pose_costs_f32 above, word for word (the correct bilinear blend, off_map,
+ * the clamped projection parameter, P = 1, zero-length segments); any sample NOT < lethal makes J[b] = +inf whatever w_map is.  goal: two
+ * floats in DEVICE memory.  roll = atan2(r1, r2), pitch = asin(clamp(-r0, -1, 1)) with r = Rs[b,t,2,:] / |Rs[b,t,2,:]|, the NORMALISED third
+ * row -- NOT the nearest-rotation projection the path-cost rollout applies (MfRolloutDesc.cost_project): the default integrator's R drifts
+ * away from a rotation, and normalising the row is the differentiable stand-in for that projection.  A row of norm 0 gives a NaN term, as a
+ * NaN pose does; the terms are summed by IEEE rules (a NaN term makes the cost NaN, whatever its weight).
+ *   costs[b] = J[b];  terms[b] = (map, xtrack, goal, incl), the four unweighted terms (map = +inf for a lethal rollout)
+ *   gXs / gRs (both given or both NULL: value only): gcosts[b] dJ[b]/dXs and gcosts[b] dJ[b]/dRs (gcosts NULL = ones), DENSE in the
+ *   strides of Xs / Rs: the rows of the steps that are not kept are written as zeros, so that mf_rollout_bwd_* takes both buffers as its
+ *   upstream gradients as they are.
+ * The gradient is that of the finite expression: max_n -> the first maximum (smallest n on a tie); the nearest segment -> the smallest k
+ * on a tie; |.| has derivative 0 at 0, and so have a zero path distance and a zero goal distance; an off-map sample and a clamped pitch
+ * have zero gradient; a lethal rollout keeps the gradient of its finite map term (it is what pushes the rollout out: only its VALUE is
+ * +inf).  Every (b, p) owns its gradient rows: no float atomics, nothing accumulated across threads, a fixed summation order -- results
+ * are bit-identical from call to call and between the rollout's time-major views and a contiguous copy.
+ * A NULL cost_map requires w_map == 0, P == 0 a NULL path and w_path == 0 (terms exactly 0, not evaluated).  One launch on the caller's
+ * stream, nothing read on the host (capturable): one workgroup of 256 threads per rollout, a 16-lane DPP row per kept pose (the lanes
+ * of a row deal the footprint points and the path's segments among themselves; maximum and minimum travel the row WITH their index).
+ * Limits: N <= 1024, P <= 256, H * W and the index range of the pose rows below 2^31. */
+typedef struct MfTrajObjDesc {
+  int32_t B, T, N, P;             /* rollouts, steps, footprint points, path vertices (0: no path term) */
+  int32_t H, W;                   /* cost map cells */
+  int32_t pose_stride, reserved;  /* >= 1 */
+  int64_t x_stride_b, x_stride_t; /* Xs[b*sb + t*st + c], c < 3 (elements); gXs likewise */
+  int64_t r_stride_b, r_stride_t; /* Rs[b*sb + t*st + 3*i + j]; gRs likewise */
+  float grid_res, d_max, lethal, off_map;
+  float w_map, w_path, w_goal, w_incl;
+} MfTrajObjDesc;
+int mf_traj_objective_f32(const MfTrajObjDesc* desc, const float* Xs, const float* Rs, const float* points /* [N][3] body frame */,
+                          const float* cost_map /* [H][W] or NULL */, const float* path /* [P][2] or NULL iff P == 0 */,
+                          const float* goal /* [2], device */, const float* gcosts /* [B] or NULL */, float* costs /* [B] */,
+                          float* terms /* [B][4] or NULL */, float* gXs, float* gRs, void* hip_stream);
+
+/* ---- Gradient descent on K control sequences: Adam + per-sequence best-so-far, ONE launch per iteration -------------------------------
+ * controls / grad / m / v / best_controls [K][T][2] contiguous, costs / best_cost [K], best_iter [K] int32, history [max_iters][K],
+ * state int32 [2] = (step, ticket), at reset (0, 0); best_cost = +inf, best_iter = -1, history = NaN at reset.  One workgroup of 256
+ * threads per sequence k, its 2 T elements in trips of 256.  With i = state[0], in this order:
+ *   1. history[i][k] = costs[k] while i < max_iters (beyond that the write is dropped and the step keeps counting)
+ *   2. costs[k] < best_cost[k] (strict: a tie, a NaN and +inf never improve): best_controls[k] = controls[k] BEFORE this update -- the
+ *      controls the cost belongs to (mf_terrain_fit_update_* snapshots AFTER the update, a quirk of the reference's loop that has no
+ *      counterpart here) --, best_cost[k] = costs[k], best_iter[k] = i
+ *   3. costs[k] is NaN, or any of the 2 T entries of grad[k] is not finite: controls[k], m[k], v[k] stay untouched in this iteration
+ *      (decided for the whole sequence, in one pass over the row ahead of any store)
+ *   4. else torch.optim.Adam's default single-tensor step as mf_terrain_fit_update_* writes it out (ATen's order of operations, rounded
+ *      op by op; bias corrections from t = i + 1 in double on the device), lr = lr[channel]
+ *   5. controls = min(max(controls, lo[channel]), hi[channel])   (the moments never see the projection)
+ * state[0] = i + 1 is committed by the workgroup that draws the last ticket (as mf_terrain_fit_update_*).  Calls that share a state
+ * must be ordered on one stream; no entry synchronises or allocates (capturable). */
+typedef struct MfRefineDesc {
+  int32_t K, T;                   /* sequences, steps */
+  int32_t max_iters, reserved;    /* rows of `history` (>= 0; 0: history may be NULL) */
+  double lr[2];                   /* (v, w); >= 0 */
+  double beta1, beta2;            /* in [0, 1) */
+  double eps;                     /* > 0 */
+  float lo[2], hi[2];             /* control limits of (v, w), lo <= hi (either may be infinite) */
+} MfRefineDesc;
+int mf_control_refine_update_f32(const MfRefineDesc* desc, float* controls, const float* grad, const float* costs, float* m, float* v,
+                                 float* best_controls, float* best_cost, int32_t* best_iter, float* history, int32_t* state,
+                                 void* hip_stream);
+
 /* Text of the calling thread's last error ("" if none).  THREAD-LOCAL: host threads driving different streams each read the message
  * of their own failed call (the reference raises a Python exception in the calling thread, dphysics.py:575,579 asserts). */
 const char* mf_last_error(void);

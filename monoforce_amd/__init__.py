@@ -26,4 +26,7 @@ def __getattr__(name):
     if name == 'TerrainFitter':
         from .fit import TerrainFitter
         return TerrainFitter
+    if name in ('ControlRefiner', 'trajectory_objective', 'trajectory_objective_aten'):
+        from . import refine
+        return getattr(refine, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

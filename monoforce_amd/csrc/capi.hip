@@ -73,5 +73,7 @@ extern "C" int mf_sizeof(const char* name) {
   if (!strcmp(name, "MfPoseLossDesc")) return (int)sizeof(MfPoseLossDesc);
   if (!strcmp(name, "MfMapLossDesc")) return (int)sizeof(MfMapLossDesc);
   if (!strcmp(name, "MfFitDesc")) return (int)sizeof(MfFitDesc);
+  if (!strcmp(name, "MfTrajObjDesc")) return (int)sizeof(MfTrajObjDesc);
+  if (!strcmp(name, "MfRefineDesc")) return (int)sizeof(MfRefineDesc);
   return -1;
 }

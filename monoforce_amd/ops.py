@@ -20,6 +20,8 @@ Schemas (tensors on the GPU, float32 or float64; `Bz` in {1, B}: a [1,H,W] map i
                                  -> (Tensor nominal, Tensor weights, Tensor best, Tensor n_valid)
     monoforce::pose_costs(Tensor Xs, Tensor Rs, Tensor points, Tensor? cost_map, Tensor? path, Tensor? base_costs, float grid_res,
                           float d_max, float lethal, float off_map, float[] weights) -> (Tensor costs, Tensor terms)
+    monoforce::traj_objective(Tensor Xs, Tensor Rs, Tensor goal, Tensor points, Tensor? cost_map, Tensor? path, float[] weights, int pose_stride,
+                              float grid_res, float d_max, float lethal, float off_map) -> (Tensor costs, Tensor terms, Tensor gXs, Tensor gRs)
     monoforce::hm_loss(Tensor height_pred, Tensor height_gt, Tensor? weights, float? h_max) -> (Tensor loss, Tensor n_valid)
     monoforce::total_variation(Tensor heightmap) -> Tensor loss
 
@@ -43,6 +45,12 @@ are int32 [1] on the device.
 `points` [N,3] the footprint in the body frame; `cost_map` [H,W] on the nodes of z_grid; `path` [P,2]; `weights` = (map, path), each 0 when
 its input is None; `costs` [B] = base_costs + w_map map + w_path xtrack, `terms` [B,2] = (map, xtrack).  One launch.
 
+`traj_objective` (float32, autograd to `Xs` and `Rs`; monoforce_amd/csrc/traj_objective.hip, formulas in include/monoforce_hip.h at
+MfTrajObjDesc): the planner's cost of B rollouts from the FULL outputs of the rollout op, `Xs` [B,T,3] and `Rs` [B,T,3,3] read in place through
+their strides, at the steps `rollout_costs` keeps for `pose_stride`; `weights` = (map, path, goal, inclination); `costs` [B], `terms` [B,4];
+`gXs` / `gRs` are dcosts.sum()/dXs and /dRs in the strides of the inputs (the backward scales them by the upstream gradient).  One launch;
+it delegates to monoforce_amd/refine.py, which marshals the entry point (its `trajectory_objective` is the drop-in form, with the ATen route).
+
 `hm_loss` / `total_variation` (float32 or float64, autograd to `height_pred` / `heightmap`; monoforce_amd/csrc/map_losses.hip, formulas in
 include/monoforce_hip.h at MfMapLossDesc): map tensors [...,H,W], channel views and row-strided crops read in place; `loss` a scalar, `n_valid`
 int32 [1] = the cells that entered the mean.  One launch forward, one backward; both delegate to monoforce_amd/losses.py, which marshals
@@ -57,7 +65,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib, losses as _losses, rollout_launch as rl, splat as _splat
+from . import _lib, losses as _losses, refine as _refine, rollout_launch as rl, splat as _splat
 
 
 class _PoolOwner:       # the registered ops have no module to hang the persistent gradient-copy pools on
@@ -84,6 +92,8 @@ _L.define('path_costs(Tensor cost_rows, Tensor? force_cost, Tensor x_last, Tenso
 _L.define('mppi_update(Tensor costs, Tensor controls, Tensor nominal, float lam) -> (Tensor, Tensor, Tensor, Tensor)')
 _L.define('pose_costs(Tensor Xs, Tensor Rs, Tensor points, Tensor? cost_map, Tensor? path, Tensor? base_costs, float grid_res, float d_max, '
           'float lethal, float off_map, float[] weights) -> (Tensor, Tensor)')
+_L.define('traj_objective(Tensor Xs, Tensor Rs, Tensor goal, Tensor points, Tensor? cost_map, Tensor? path, float[] weights, int pose_stride, '
+          'float grid_res, float d_max, float lethal, float off_map) -> (Tensor, Tensor, Tensor, Tensor)')
 _L.define('hm_loss(Tensor height_pred, Tensor height_gt, Tensor? weights, float? h_max) -> (Tensor, Tensor)')
 _L.define('total_variation(Tensor heightmap) -> Tensor')
 
@@ -368,6 +378,34 @@ def _pose_costs(Xs, Rs, points, cost_map, path, base_costs, grid_res, d_max, let
 def _pose_costs_fake(Xs, Rs, points, cost_map, path, base_costs, grid_res, d_max, lethal, off_map, weights):
     B = Xs.shape[0]
     return Xs.new_empty(B), Xs.new_empty(B, 2)
+
+
+# ---- the planner's cost with its gradient (monoforce_amd/refine.py) ----------------------------------------------------------------------
+@torch.library.impl(_L, 'traj_objective', 'CUDA')
+def _traj_objective(Xs, Rs, goal, points, cost_map, path, weights, pose_stride, grid_res, d_max, lethal, off_map):
+    return _refine.objective_launch(Xs, Rs, goal, points, cost_map, path, weights, pose_stride, grid_res, d_max, lethal, off_map)
+
+
+def _traj_objective_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[2], output[3])
+    ctx.set_materialize_grads(False)
+
+
+def _traj_objective_backward(ctx, gcosts, _gterms, _ggXs, _ggRs):
+    none = (None,) * 12
+    if gcosts is None:
+        return none
+    gXs, gRs = ctx.saved_tensors
+    return (_refine._scaled(gXs, gcosts), _refine._scaled(gRs, gcosts)) + none[2:]
+
+
+torch.library.register_autograd('monoforce::traj_objective', _traj_objective_backward, setup_context=_traj_objective_setup, lib=_L)
+
+
+@torch.library.register_fake('monoforce::traj_objective', lib=_L)
+def _traj_objective_fake(Xs, Rs, goal, points, cost_map, path, weights, pose_stride, grid_res, d_max, lethal, off_map):
+    B = Xs.shape[0]
+    return Xs.new_empty(B), Xs.new_empty(B, 4), torch.empty_like(Xs), torch.empty_like(Rs)
 
 
 # ---- height-map losses ---------------------------------------------------------------------------------------------------------------
