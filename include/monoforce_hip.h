@@ -696,6 +696,52 @@ int mf_control_refine_update_f32(const MfRefineDesc* desc, float* controls, cons
                                  float* best_controls, float* best_cost, int32_t* best_iter, float* history, int32_t* state,
                                  void* hip_stream);
 
+/* ---- Planner cost maps from terrain: slope, roughness and step height under a disc, ONE launch ------------------------------------------
+ * (No reference equivalent: its planning node scores rollouts by inclination only and its elevation-mapping pipeline has the surface-normal
+ * filter commented out.  The result is what mf_pose_costs_f32 / mf_traj_objective_f32 take as `cost_map`.)
+ * Inputs.  z: S maps of H x W heights, element (s, h, w) at s*z_stride_s + h*z_stride_h + w (elements; unit stride along W: a squeeze(1) of
+ *   [S,1,H,W] and a row-strided crop are read in place).  valid (may be NULL): the same shape with its own strides v_*, nonzero = usable.
+ *   base (may be NULL): the same shape with its own strides b_*, a keep-out map to merge.  Scalars as C floats: grid_res > 0 (metres per
+ *   cell), lo[k] < hi[k] for k = (slope, roughness, step), unknown.  Integers: the window radius r in cells, 1 <= r <=
+ *   MF_TRAVERSABILITY_MAX_RADIUS, and min_valid >= 3.
+ * Window of cell (i, j): the cells (i + di, j + dj) with di^2 + dj^2 <= r^2 (in integers) that lie inside the map, where z is finite and,
+ *   with `valid` given, valid is nonzero.  n = their number.
+ * Known cells.  With the sums over the window  A = n sum di^2 - (sum di)^2,  B = n sum dj^2 - (sum dj)^2,  C = n sum di dj - sum di sum dj
+ *   in 64-bit integers, the cell is KNOWN iff  n >= min_valid  and  A B - C^2 > 0  (the window cells are not collinear).  This is the only
+ *   discontinuous rule of the definition, and it is decided in integers so that every implementation agrees on it exactly.  It depends on
+ *   the window, not on whether the centre cell itself is usable.
+ * Terms of a known cell.  With u = di grid_res, v = dj grid_res, the least-squares plane  z ~ zbar + a (u - ubar) + b (v - vbar)  over the
+ *   window (centred 2 x 2 normal equations):
+ *     slope     = sqrt(a^2 + b^2)                    rise over run
+ *     roughness = sqrt(sum residual^2 / n)           the residuals themselves are squared and summed, not a moment identity
+ *     step      = max z - min z over the window
+ *   An unknown cell's three terms are NaN.
+ * Cost.  ramp_k = min(max((term_k - lo[k]) / (hi[k] - lo[k]), 0), 1);  cost = max_k ramp_k for a known cell, `unknown` otherwise; with
+ *   `base`, cost = max(cost, base) wherever base is not NaN, unknown cells included.  cost is in [0,1] when `unknown` and `base` are.
+ * Outputs.  cost [S][H][W] contiguous; terms [S][3][H][W] contiguous = (slope, roughness, step), or NULL.  Every cell is STORED (plain
+ *   stores, no atomics): the buffers need not be initialised, and two launches on the same input are bit-identical.  Neither output may
+ *   alias an input.  There is no backward: cost maps feed planners.
+ * Launch.  One workgroup per tile of MF_TRAVERSABILITY_TILE^2 output cells stages the tile and a halo of r cells into LDS once (validity
+ *   folded in) and reads every window from there; S * ceil(H / TILE) * ceil(W / TILE) must be below 2^31.  The entry neither synchronises
+ *   nor allocates (capturable).  float32 centres the heights on the window mean before any product is formed; _f64 is the validation build
+ *   of the same source. */
+#define MF_TRAVERSABILITY_TILE 16
+#define MF_TRAVERSABILITY_MAX_RADIUS 16
+typedef struct MfTraversabilityDesc {
+  int32_t S, H, W;                /* maps, rows, columns */
+  int32_t r;                      /* window radius in cells */
+  int32_t min_valid, reserved;
+  int64_t z_stride_s, z_stride_h;
+  int64_t v_stride_s, v_stride_h; /* ignored when valid is NULL */
+  int64_t b_stride_s, b_stride_h; /* ignored when base is NULL */
+  float grid_res, unknown;
+  float lo[3], hi[3];             /* (slope [rise/run], roughness [m], step [m]) */
+} MfTraversabilityDesc;
+int mf_traversability_f32(const MfTraversabilityDesc* desc, const float* z, const float* valid, const float* base, float* cost, float* terms,
+                          void* hip_stream);
+int mf_traversability_f64(const MfTraversabilityDesc* desc, const double* z, const double* valid, const double* base, double* cost,
+                          double* terms, void* hip_stream);
+
 /* Text of the calling thread's last error ("" if none).  THREAD-LOCAL: host threads driving different streams each read the message
  * of their own failed call (the reference raises a Python exception in the calling thread, dphysics.py:575,579 asserts). */
 const char* mf_last_error(void);

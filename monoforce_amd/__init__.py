@@ -29,4 +29,7 @@ def __getattr__(name):
     if name in ('ControlRefiner', 'trajectory_objective', 'trajectory_objective_aten'):
         from . import refine
         return getattr(refine, name)
+    if name in ('TraversabilityMap', 'traversability_map', 'traversability_map_aten'):
+        from . import costmap
+        return getattr(costmap, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

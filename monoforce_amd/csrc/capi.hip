@@ -75,5 +75,36 @@ extern "C" int mf_sizeof(const char* name) {
   if (!strcmp(name, "MfFitDesc")) return (int)sizeof(MfFitDesc);
   if (!strcmp(name, "MfTrajObjDesc")) return (int)sizeof(MfTrajObjDesc);
   if (!strcmp(name, "MfRefineDesc")) return (int)sizeof(MfRefineDesc);
+  if (!strcmp(name, "MfTraversabilityDesc")) return (int)sizeof(MfTraversabilityDesc);
   return -1;
+}
+
+// ---- mf_traversability_*: the descriptor is validated here (no device needed), the launch is traversability.hip's
+namespace mf {
+template <typename S>
+int traversability_launch(const MfTraversabilityDesc* d, const S* z, const S* valid, const S* base, S* cost, S* terms, hipStream_t st);
+
+template <typename S>
+static int traversability(const MfTraversabilityDesc* d, const S* z, const S* valid, const S* base, S* cost, S* terms, void* st) {
+  MF_REQUIRE(d, MF_ERR_INVALID, "traversability: null descriptor");
+  MF_REQUIRE(d->S > 0 && d->H > 0 && d->W > 0, MF_ERR_INVALID, "traversability: S, H, W must be positive");
+  MF_REQUIRE(z && cost, MF_ERR_INVALID, "traversability: null input (z and cost are required)");
+  MF_REQUIRE(d->r >= 1 && d->r <= MF_TRAVERSABILITY_MAX_RADIUS, MF_ERR_INVALID,
+             "traversability: the window radius r must be in 1.." + std::to_string(MF_TRAVERSABILITY_MAX_RADIUS) + " cells, got " +
+                 std::to_string(d->r));
+  MF_REQUIRE(d->min_valid >= 3, MF_ERR_INVALID, "traversability: min_valid must be at least 3 (a plane has three parameters)");
+  MF_REQUIRE(d->grid_res > 0.f, MF_ERR_INVALID, "traversability: grid_res must be positive");
+  for (int k = 0; k < 3; ++k)
+    MF_REQUIRE(d->hi[k] > d->lo[k], MF_ERR_INVALID, "traversability: hi must be above lo for every term (slope, roughness, step)");
+  return traversability_launch<S>(d, z, valid, base, cost, terms, (hipStream_t)st);
+}
+}  // namespace mf
+
+extern "C" int mf_traversability_f32(const MfTraversabilityDesc* d, const float* z, const float* valid, const float* base, float* cost,
+                                     float* terms, void* s) {
+  return mf::traversability<float>(d, z, valid, base, cost, terms, s);
+}
+extern "C" int mf_traversability_f64(const MfTraversabilityDesc* d, const double* z, const double* valid, const double* base, double* cost,
+                                     double* terms, void* s) {
+  return mf::traversability<double>(d, z, valid, base, cost, terms, s);
 }

@@ -24,6 +24,8 @@ Schemas (tensors on the GPU, float32 or float64; `Bz` in {1, B}: a [1,H,W] map i
                               float grid_res, float d_max, float lethal, float off_map) -> (Tensor costs, Tensor terms, Tensor gXs, Tensor gRs)
     monoforce::hm_loss(Tensor height_pred, Tensor height_gt, Tensor? weights, float? h_max) -> (Tensor loss, Tensor n_valid)
     monoforce::total_variation(Tensor heightmap) -> Tensor loss
+    monoforce::traversability(Tensor z, Tensor? valid, Tensor? base, float grid_res, int radius_cells, float[] lo, float[] hi, float unknown,
+                              int min_valid, bool return_terms) -> (Tensor cost, Tensor terms)
 
 `consts` = [mass, gravity, stiffness, damping, grid_res, d_max, dt, omega_max, robot_size_y(, traj_sim_time)]; `part_id[N]` int32
 (index of the last driving mask holding the point, -1 = not driving); `Iinv` [3,3] on the HOST (nine scalars of the launch
@@ -56,6 +58,12 @@ include/monoforce_hip.h at MfMapLossDesc): map tensors [...,H,W], channel views 
 int32 [1] = the cells that entered the mean.  One launch forward, one backward; both delegate to monoforce_amd/losses.py, which marshals
 the entry points (its `hm_loss` / `total_variation` are the drop-in forms, with the ATen route for CPU tensors).
 
+`traversability` (float32 or float64, no autograd; monoforce_amd/csrc/traversability.hip, definition in include/monoforce_hip.h at
+MfTraversabilityDesc): `z` [H,W] or [S,H,W] with unit stride along W, read in place (as `valid` and `base` of the same shape); `lo` / `hi` the
+ramps of (slope, roughness, step); `cost` has z's shape, `terms` is [..,3,H,W] (empty without `return_terms`).  One launch; it delegates to
+monoforce_amd/costmap.py, which marshals the entry point (`traversability_into` below writes caller-owned buffers; `traversability_map` is
+the form with the radius in metres and the ATen route for CPU tensors).
+
 The rollout ops and `DPhysics`'s own autograd function (monoforce_amd/dphysics.py: more options -- articulated bodies, path costs,
 strided controls) launch through the same marshalling (monoforce_amd/rollout_launch.py), the splat ops and `voxel_pooling` likewise
 (monoforce_amd/splat.py); only the MPPI and pose-cost entry points, which have no other caller, are marshalled here (`_lib.launch`).
@@ -65,7 +73,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib, losses as _losses, refine as _refine, rollout_launch as rl, splat as _splat
+from . import _lib, costmap as _costmap, losses as _losses, refine as _refine, rollout_launch as rl, splat as _splat
 
 
 class _PoolOwner:       # the registered ops have no module to hang the persistent gradient-copy pools on
@@ -96,6 +104,8 @@ _L.define('traj_objective(Tensor Xs, Tensor Rs, Tensor goal, Tensor points, Tens
           'float grid_res, float d_max, float lethal, float off_map) -> (Tensor, Tensor, Tensor, Tensor)')
 _L.define('hm_loss(Tensor height_pred, Tensor height_gt, Tensor? weights, float? h_max) -> (Tensor, Tensor)')
 _L.define('total_variation(Tensor heightmap) -> Tensor')
+_L.define('traversability(Tensor z, Tensor? valid, Tensor? base, float grid_res, int radius_cells, float[] lo, float[] hi, float unknown, '
+          'int min_valid, bool return_terms) -> (Tensor, Tensor)')
 
 
 def _time_grid(consts, T, dt, dev):
@@ -471,6 +481,27 @@ torch.library.register_autograd('monoforce::total_variation', _total_variation_b
 @torch.library.register_fake('monoforce::total_variation', lib=_L)
 def _total_variation_fake(heightmap):
     return heightmap.new_empty(())
+
+
+# ---- planner cost maps from terrain (monoforce_amd/costmap.py) ------------------------------------------------------------------------------
+traversability_into = _costmap.traversability_into      # the op writing caller-owned `cost` / `terms` buffers
+
+
+def _terms_shape(z):
+    return tuple(z.shape[:-2]) + (3,) + tuple(z.shape[-2:])
+
+
+@torch.library.impl(_L, 'traversability', 'CUDA')
+def _traversability(z, valid, base, grid_res, radius_cells, lo, hi, unknown, min_valid, return_terms):
+    cost = torch.empty(z.shape, dtype=z.dtype, device=z.device)
+    terms = torch.empty(_terms_shape(z), dtype=z.dtype, device=z.device) if return_terms else None
+    _costmap.traversability_into(z.detach(), valid, base, grid_res, radius_cells, list(lo), list(hi), unknown, min_valid, cost, terms)
+    return cost, (terms if return_terms else torch.empty(0, dtype=z.dtype, device=z.device))
+
+
+@torch.library.register_fake('monoforce::traversability', lib=_L)
+def _traversability_fake(z, valid, base, grid_res, radius_cells, lo, hi, unknown, min_valid, return_terms):
+    return z.new_empty(z.shape), z.new_empty(_terms_shape(z) if return_terms else (0,))
 
 
 # ---- functional entries ------------------------------------------------------------------------------------------------------
