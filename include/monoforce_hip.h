@@ -742,6 +742,78 @@ int mf_traversability_f32(const MfTraversabilityDesc* desc, const float* z, cons
 int mf_traversability_f64(const MfTraversabilityDesc* desc, const double* z, const double* valid, const double* base, double* cost,
                           double* terms, void* hip_stream);
 
+/* ---- Global routes on a cost map: the cost-to-go field towards a goal and the optimal route as a polyline ---------------------------------
+ * (No reference equivalent: its planning node follows a hand-given goal.  The inputs are the `cost_map` of mf_pose_costs_f32 -- e.g. the
+ * result of mf_traversability_* -- and the result is the `path` [P][2] mf_pose_costs_f32 / mf_traj_objective_f32 read.)
+ * Grid.  cost: S maps of H x W node costs, element (s, i, j) at s*c_stride_s + i*c_stride_h + j (elements; unit stride along W, read in
+ *   place), with the convention of MfPoseCostDesc: the first axis is x, node (i, j) sits at x = i*grid_res - d_max, y = j*grid_res - d_max.
+ * Arithmetic.  The scalar type T of the entry point (_f32: float, _f64: double).  grid_res, d_max, lethal and alpha are carried as C floats
+ *   and converted to T once.  EVERY operation below is rounded separately in T (the translation unit is built with -ffp-contract=off).
+ * Passable.  A node is passable iff its cost is finite and < lethal.  NaN, +-inf and costs >= lethal are walls.
+ * Factor.  s[c] = 1 + alpha * max(cost[c], 0)   (0 <= alpha < inf; one multiply, one add).
+ * Moves.  Eight neighbours (di, dj) in this order:  (-1,0) (1,0) (0,-1) (0,1) (-1,-1) (-1,1) (1,-1) (1,1).  A move needs both ends on the
+ *   map and passable; a diagonal move (di, dj) from (i, j) needs (i + di, j) and (i, j + dj) passable as well (no corner of a wall is cut).
+ * Edge weight.  w(u, v) = len * ((s[u] + s[v]) * 0.5),  len = grid_res for an axial move and fl(grid_res * 1.4142135623730951) for a
+ *   diagonal one.  w(u, v) = w(v, u) to the bit.
+ * Field.  The goal node is (round((g_x + d_max) / grid_res), round((g_y + d_max) / grid_res)), ties to even, for the goal position g of
+ *   the map (goal [S][2], T).  d[goal node] = 0; elsewhere d[v] = min over the permitted neighbours u of fl(d[u] + w(u, v)); +inf on
+ *   impassable and unreachable nodes.  Rounded addition is monotone and every weight is positive, so this fixed point is unique and every
+ *   relaxation order reaches it: the field is bit-equal to a heap Dijkstra in T.  A goal off the map (or NaN) or on an impassable node:
+ *   the whole field is +inf and status gets MF_ROUTE_GOAL_BLOCKED.
+ * mf_cost_to_go_*.  field [S][H][W] contiguous, fully written.  status [S] and rounds_used [S] int32, written (not accumulated) by the call.
+ *   One initialisation launch and n_rounds launches of one round kernel; a workgroup owns a tile of MF_ROUTE_TILE^2 nodes, relaxes it in LDS
+ *   against a one-node halo until it stops changing, and wakes the neighbour tiles whose halo it changed for the next round; tiles nobody
+ *   woke, and every tile once a round changed nothing, leave at once (round 0 starts from the tiles that hold the goal node or have it in
+ *   their halo).  No workgroup waits on another: all ordering across workgroups is the
+ *   launch boundary.  rounds_used = the rounds that changed the field.  MF_ROUTE_NOT_CONVERGED iff the last round still changed it; the
+ *   field is then an upper bound of the true one everywhere.  work: int32 scratch of at least mf_cost_to_go_work_ints(desc) words, which
+ *   the call initialises itself.  A map without walls needs about tiles_h + tiles_w rounds, a serpentine one round per tile border its
+ *   route crosses; empty rounds cost a launch each.
+ * Route.  v_0 = the nearest node to the start position (start [S][2], T; rounded as the goal).  v_(k+1) = argmin over the permitted
+ *   neighbours u of v_k of fl(d[u] + w(u, v_k)), ties to the earlier neighbour in the order above; the walk ends at the goal node.
+ * mf_extract_route_*.  field as above and the cost it was made from (w is recomputed).  nodes [S][max_nodes] int32 = i*W + j, the first
+ *   n_nodes [S] of each row written; route_cost [S] (T) = d[v_0]; path [S][P][2] FLOAT always (what the planners read): with L = n_nodes,
+ *   vertex p is the position of nodes[(p * (L - 1)) / (P - 1)] (integer division), coordinates fl(fl(i * grid_res) - d_max) in float.
+ *   status [S] int32 is read-modify-written: the two field bits are kept, the two route bits are set or cleared.
+ *     start off the map (or NaN) or d[v_0] not finite: MF_ROUTE_START_UNREACHABLE, n_nodes = 0, route_cost = +inf, every vertex = the start
+ *       position as given (converted to float);
+ *     the walk reaches max_nodes nodes before the goal, or finds no neighbour with a finite value (a field that is not this cost's):
+ *       MF_ROUTE_TRUNCATED, the path is resampled from the nodes walked;
+ *     L = 1 (the start node is the goal node): P copies of it.
+ *   One launch, one wave per map: eight lanes fetch the eight candidates, a DPP minimum carrying the neighbour's index picks the next node.
+ * Neither entry synchronises, allocates or reads anything on the host (capturable); H * W must be below 2^31. */
+#define MF_ROUTE_TILE 32
+#define MF_ROUTE_MAX_VERTICES 256
+#define MF_ROUTE_GOAL_BLOCKED 1
+#define MF_ROUTE_NOT_CONVERGED 2
+#define MF_ROUTE_START_UNREACHABLE 4
+#define MF_ROUTE_TRUNCATED 8
+typedef struct MfCostToGoDesc {
+  int32_t S, H, W;                /* maps, rows (x), columns (y) */
+  int32_t n_rounds;               /* launches of the round kernel, >= 1 */
+  int64_t c_stride_s, c_stride_h; /* strides of cost in elements */
+  float grid_res, d_max;
+  float lethal, alpha;            /* lethal may be +inf (only non-finite costs are walls); alpha finite, >= 0 */
+} MfCostToGoDesc;
+typedef struct MfRouteDesc {
+  int32_t S, H, W;
+  int32_t P;                      /* vertices of the polyline, 2 .. MF_ROUTE_MAX_VERTICES */
+  int32_t max_nodes, reserved;    /* row length of nodes, >= 2 */
+  int64_t c_stride_s, c_stride_h;
+  float grid_res, d_max;
+  float lethal, alpha;
+} MfRouteDesc;
+/* int32 words of `work` for this descriptor: S * (2 * tiles + n_rounds) with tiles = ceil(H / TILE) * ceil(W / TILE); -1 for a bad descriptor */
+long long mf_cost_to_go_work_ints(const MfCostToGoDesc* desc);
+int mf_cost_to_go_f32(const MfCostToGoDesc* desc, const float* cost, const float* goal, float* field, int32_t* status, int32_t* rounds_used,
+                      int32_t* work, void* hip_stream);
+int mf_cost_to_go_f64(const MfCostToGoDesc* desc, const double* cost, const double* goal, double* field, int32_t* status,
+                      int32_t* rounds_used, int32_t* work, void* hip_stream);
+int mf_extract_route_f32(const MfRouteDesc* desc, const float* field, const float* cost, const float* start, const float* goal, int32_t* nodes,
+                         int32_t* n_nodes, float* route_cost, float* path, int32_t* status, void* hip_stream);
+int mf_extract_route_f64(const MfRouteDesc* desc, const double* field, const double* cost, const double* start, const double* goal,
+                         int32_t* nodes, int32_t* n_nodes, double* route_cost, float* path, int32_t* status, void* hip_stream);
+
 /* Text of the calling thread's last error ("" if none).  THREAD-LOCAL: host threads driving different streams each read the message
  * of their own failed call (the reference raises a Python exception in the calling thread, dphysics.py:575,579 asserts). */
 const char* mf_last_error(void);

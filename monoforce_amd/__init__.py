@@ -32,4 +32,7 @@ def __getattr__(name):
     if name in ('TraversabilityMap', 'traversability_map', 'traversability_map_aten'):
         from . import costmap
         return getattr(costmap, name)
+    if name in ('RoutePlanner', 'cost_to_go', 'extract_route', 'cost_to_go_aten', 'extract_route_host'):
+        from . import route
+        return getattr(route, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -76,6 +76,8 @@ extern "C" int mf_sizeof(const char* name) {
   if (!strcmp(name, "MfTrajObjDesc")) return (int)sizeof(MfTrajObjDesc);
   if (!strcmp(name, "MfRefineDesc")) return (int)sizeof(MfRefineDesc);
   if (!strcmp(name, "MfTraversabilityDesc")) return (int)sizeof(MfTraversabilityDesc);
+  if (!strcmp(name, "MfCostToGoDesc")) return (int)sizeof(MfCostToGoDesc);
+  if (!strcmp(name, "MfRouteDesc")) return (int)sizeof(MfRouteDesc);
   return -1;
 }
 
@@ -107,4 +109,71 @@ extern "C" int mf_traversability_f32(const MfTraversabilityDesc* d, const float*
 extern "C" int mf_traversability_f64(const MfTraversabilityDesc* d, const double* z, const double* valid, const double* base, double* cost,
                                      double* terms, void* s) {
   return mf::traversability<double>(d, z, valid, base, cost, terms, s);
+}
+
+// ---- mf_cost_to_go_* / mf_extract_route_*: the descriptors are validated here (no device needed), the launches are cost_to_go.hip's
+namespace mf {
+template <typename S>
+int cost_to_go_launch(const MfCostToGoDesc* d, const S* cost, const S* goal, S* field, int32_t* status, int32_t* rounds_used, int32_t* work,
+                      hipStream_t st);
+template <typename S>
+int extract_route_launch(const MfRouteDesc* d, const S* field, const S* cost, const S* start, const S* goal, int32_t* nodes, int32_t* n_nodes,
+                         S* route_cost, float* path, int32_t* status, hipStream_t st);
+
+static int cost_to_go_desc_ok(const MfCostToGoDesc* d) {
+  MF_REQUIRE(d, MF_ERR_INVALID, "cost_to_go: null descriptor");
+  MF_REQUIRE(d->S > 0 && d->H > 0 && d->W > 0, MF_ERR_INVALID, "cost_to_go: S, H, W must be positive");
+  MF_REQUIRE((long long)d->H * d->W < (1ll << 31), MF_ERR_INVALID, "cost_to_go: H * W must be below 2^31 (nodes are int32 indices)");
+  MF_REQUIRE(d->grid_res > 0.f, MF_ERR_INVALID, "cost_to_go: grid_res must be positive");
+  MF_REQUIRE(d->alpha >= 0.f && d->alpha <= 3.402823466e38f, MF_ERR_INVALID, "cost_to_go: alpha must be finite and not negative");
+  MF_REQUIRE(d->n_rounds >= 1, MF_ERR_INVALID, "cost_to_go: n_rounds must be at least 1, got " + std::to_string(d->n_rounds));
+  return MF_OK;
+}
+
+template <typename S>
+static int cost_to_go(const MfCostToGoDesc* d, const S* cost, const S* goal, S* field, int32_t* status, int32_t* rounds_used, int32_t* work,
+                      void* st) {
+  if (int rc = cost_to_go_desc_ok(d)) return rc;
+  MF_REQUIRE(cost && goal && field && status && rounds_used && work, MF_ERR_INVALID,
+             "cost_to_go: null input (cost, goal, field, status, rounds_used and work are required)");
+  return cost_to_go_launch<S>(d, cost, goal, field, status, rounds_used, work, (hipStream_t)st);
+}
+
+template <typename S>
+static int extract_route(const MfRouteDesc* d, const S* field, const S* cost, const S* start, const S* goal, int32_t* nodes, int32_t* n_nodes,
+                         S* route_cost, float* path, int32_t* status, void* st) {
+  MF_REQUIRE(d, MF_ERR_INVALID, "extract_route: null descriptor");
+  MF_REQUIRE(d->S > 0 && d->H > 0 && d->W > 0, MF_ERR_INVALID, "extract_route: S, H, W must be positive");
+  MF_REQUIRE((long long)d->H * d->W < (1ll << 31), MF_ERR_INVALID, "extract_route: H * W must be below 2^31 (nodes are int32 indices)");
+  MF_REQUIRE(d->P >= 2 && d->P <= MF_ROUTE_MAX_VERTICES, MF_ERR_INVALID,
+             "extract_route: P must be in 2.." + std::to_string(MF_ROUTE_MAX_VERTICES) + " vertices, got " + std::to_string(d->P));
+  MF_REQUIRE(d->max_nodes >= 2, MF_ERR_INVALID, "extract_route: max_nodes must be at least 2, got " + std::to_string(d->max_nodes));
+  MF_REQUIRE(d->grid_res > 0.f, MF_ERR_INVALID, "extract_route: grid_res must be positive");
+  MF_REQUIRE(d->alpha >= 0.f && d->alpha <= 3.402823466e38f, MF_ERR_INVALID, "extract_route: alpha must be finite and not negative");
+  MF_REQUIRE(field && cost && start && goal && nodes && n_nodes && route_cost && path && status, MF_ERR_INVALID,
+             "extract_route: null input (every pointer is required)");
+  return extract_route_launch<S>(d, field, cost, start, goal, nodes, n_nodes, route_cost, path, status, (hipStream_t)st);
+}
+}  // namespace mf
+
+extern "C" long long mf_cost_to_go_work_ints(const MfCostToGoDesc* d) {
+  if (mf::cost_to_go_desc_ok(d) != MF_OK) return -1;
+  const long long tiles = (long long)((d->H + MF_ROUTE_TILE - 1) / MF_ROUTE_TILE) * ((d->W + MF_ROUTE_TILE - 1) / MF_ROUTE_TILE);
+  return (long long)d->S * (2 * tiles + d->n_rounds);
+}
+extern "C" int mf_cost_to_go_f32(const MfCostToGoDesc* d, const float* cost, const float* goal, float* field, int32_t* status,
+                                 int32_t* rounds_used, int32_t* work, void* s) {
+  return mf::cost_to_go<float>(d, cost, goal, field, status, rounds_used, work, s);
+}
+extern "C" int mf_cost_to_go_f64(const MfCostToGoDesc* d, const double* cost, const double* goal, double* field, int32_t* status,
+                                 int32_t* rounds_used, int32_t* work, void* s) {
+  return mf::cost_to_go<double>(d, cost, goal, field, status, rounds_used, work, s);
+}
+extern "C" int mf_extract_route_f32(const MfRouteDesc* d, const float* field, const float* cost, const float* start, const float* goal,
+                                    int32_t* nodes, int32_t* n_nodes, float* route_cost, float* path, int32_t* status, void* s) {
+  return mf::extract_route<float>(d, field, cost, start, goal, nodes, n_nodes, route_cost, path, status, s);
+}
+extern "C" int mf_extract_route_f64(const MfRouteDesc* d, const double* field, const double* cost, const double* start, const double* goal,
+                                    int32_t* nodes, int32_t* n_nodes, double* route_cost, float* path, int32_t* status, void* s) {
+  return mf::extract_route<double>(d, field, cost, start, goal, nodes, n_nodes, route_cost, path, status, s);
 }

@@ -26,6 +26,10 @@ Schemas (tensors on the GPU, float32 or float64; `Bz` in {1, B}: a [1,H,W] map i
     monoforce::total_variation(Tensor heightmap) -> Tensor loss
     monoforce::traversability(Tensor z, Tensor? valid, Tensor? base, float grid_res, int radius_cells, float[] lo, float[] hi, float unknown,
                               int min_valid, bool return_terms) -> (Tensor cost, Tensor terms)
+    monoforce::cost_to_go(Tensor cost_map, Tensor goal, float grid_res, float d_max, float lethal, float alpha, int n_rounds)
+                              -> (Tensor field, Tensor status, Tensor rounds_used)
+    monoforce::extract_route(Tensor field, Tensor cost_map, Tensor start, Tensor goal, float grid_res, float d_max, float lethal, float alpha,
+                              int n_vertices, int max_nodes) -> (Tensor path, Tensor nodes, Tensor n_nodes, Tensor route_cost, Tensor status)
 
 `consts` = [mass, gravity, stiffness, damping, grid_res, d_max, dt, omega_max, robot_size_y(, traj_sim_time)]; `part_id[N]` int32
 (index of the last driving mask holding the point, -1 = not driving); `Iinv` [3,3] on the HOST (nine scalars of the launch
@@ -64,6 +68,11 @@ ramps of (slope, roughness, step); `cost` has z's shape, `terms` is [..,3,H,W] (
 monoforce_amd/costmap.py, which marshals the entry point (`traversability_into` below writes caller-owned buffers; `traversability_map` is
 the form with the radius in metres and the ATen route for CPU tensors).
 
+`cost_to_go` / `extract_route` (float32 or float64, no autograd; monoforce_amd/csrc/cost_to_go.hip, definition in include/monoforce_hip.h at
+MfCostToGoDesc): `cost_map` [H,W] or [S,H,W] with unit stride along W, read in place; `goal` / `start` [2] or [S,2]; `n_rounds` / `max_nodes`
+<= 0 ask for the defaults.  `field` has cost_map's shape, `status` / `rounds_used` / `n_nodes` are int32 [S], `path` float32 [S,P,2], `nodes`
+int32 [S,max_nodes].  Both delegate to monoforce_amd/route.py, which marshals the entry points (`RoutePlanner` there owns static buffers).
+
 The rollout ops and `DPhysics`'s own autograd function (monoforce_amd/dphysics.py: more options -- articulated bodies, path costs,
 strided controls) launch through the same marshalling (monoforce_amd/rollout_launch.py), the splat ops and `voxel_pooling` likewise
 (monoforce_amd/splat.py); only the MPPI and pose-cost entry points, which have no other caller, are marshalled here (`_lib.launch`).
@@ -73,7 +82,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib, costmap as _costmap, losses as _losses, refine as _refine, rollout_launch as rl, splat as _splat
+from . import _lib, costmap as _costmap, losses as _losses, refine as _refine, rollout_launch as rl, route as _route, splat as _splat
 
 
 class _PoolOwner:       # the registered ops have no module to hang the persistent gradient-copy pools on
@@ -106,6 +115,9 @@ _L.define('hm_loss(Tensor height_pred, Tensor height_gt, Tensor? weights, float?
 _L.define('total_variation(Tensor heightmap) -> Tensor')
 _L.define('traversability(Tensor z, Tensor? valid, Tensor? base, float grid_res, int radius_cells, float[] lo, float[] hi, float unknown, '
           'int min_valid, bool return_terms) -> (Tensor, Tensor)')
+_L.define('cost_to_go(Tensor cost_map, Tensor goal, float grid_res, float d_max, float lethal, float alpha, int n_rounds) -> (Tensor, Tensor, Tensor)')
+_L.define('extract_route(Tensor field, Tensor cost_map, Tensor start, Tensor goal, float grid_res, float d_max, float lethal, float alpha, '
+          'int n_vertices, int max_nodes) -> (Tensor, Tensor, Tensor, Tensor, Tensor)')
 
 
 def _time_grid(consts, T, dt, dev):
@@ -502,6 +514,34 @@ def _traversability(z, valid, base, grid_res, radius_cells, lo, hi, unknown, min
 @torch.library.register_fake('monoforce::traversability', lib=_L)
 def _traversability_fake(z, valid, base, grid_res, radius_cells, lo, hi, unknown, min_valid, return_terms):
     return z.new_empty(z.shape), z.new_empty(_terms_shape(z) if return_terms else (0,))
+
+
+# ---- global routes on a cost map (monoforce_amd/route.py) ------------------------------------------------------------------------------------
+@torch.library.impl(_L, 'cost_to_go', 'CUDA')
+def _cost_to_go(cost_map, goal, grid_res, d_max, lethal, alpha, n_rounds):
+    return _route.cost_to_go(cost_map, goal, grid_res, d_max, lethal, alpha, n_rounds if n_rounds > 0 else None, return_status=True)
+
+
+@torch.library.register_fake('monoforce::cost_to_go', lib=_L)
+def _cost_to_go_fake(cost_map, goal, grid_res, d_max, lethal, alpha, n_rounds):
+    S = cost_map.shape[0] if cost_map.dim() == 3 else 1
+    return cost_map.new_empty(cost_map.shape), cost_map.new_empty((S,), dtype=torch.int32), cost_map.new_empty((S,), dtype=torch.int32)
+
+
+@torch.library.impl(_L, 'extract_route', 'CUDA')
+def _extract_route(field, cost_map, start, goal, grid_res, d_max, lethal, alpha, n_vertices, max_nodes):
+    out = _route.extract_route(field, cost_map, start, goal, grid_res, d_max, lethal, alpha, n_vertices, max_nodes if max_nodes > 0 else None)
+    path = out['path'] if cost_map.dim() == 3 else out['path'][None]
+    return path, out['nodes'], out['n_nodes'], out['route_cost'], out['status']
+
+
+@torch.library.register_fake('monoforce::extract_route', lib=_L)
+def _extract_route_fake(field, cost_map, start, goal, grid_res, d_max, lethal, alpha, n_vertices, max_nodes):
+    S = cost_map.shape[0] if cost_map.dim() == 3 else 1
+    n = max_nodes if max_nodes > 0 else cost_map.shape[-2] * cost_map.shape[-1]
+    i32 = dict(dtype=torch.int32)
+    return (cost_map.new_empty((S, n_vertices, 2), dtype=torch.float32), cost_map.new_empty((S, n), **i32), cost_map.new_empty((S,), **i32),
+            cost_map.new_empty((S,)), cost_map.new_empty((S,), **i32))
 
 
 # ---- functional entries ------------------------------------------------------------------------------------------------------
