@@ -9,6 +9,35 @@
 
 namespace mf {
 
+namespace cp {
+// ---- forms of the step loop's lane algebra that take their cross-lane operand INSIDE the arithmetic instruction ----
+// cp_wraw (rollout_cp_common.h) on the torque sum as cross_pre leaves it -- component c in lane (c + 1) % 3 of the quad: the rotation
+// home is composed into the broadcast selectors (the sums over the points add the same values in the same order, lane position by
+// lane position), and the two fused multiply-adds are v_fmac_f32 with the broadcast as their DPP operand -- the same operations on
+// the same values in the same order, so the same bits, without the two moves that bring a broadcast into a register of its own
+// (the compiler's DPP combiner leaves such a move in front of an instruction whose accumulator is tied to its result).
+// Not volatile: scheduled like any other instruction; ONE statement, because the compiler separates a statement that reads what
+// another one wrote by a wait state it cannot know to be unnecessary.  It does not see into the text for the two wait states a DPP
+// read of a fresh VALU result needs either: the product in front is the compiler's own instruction, reads Trot through DPP too and
+// feeds the accumulator, so Trot is at least three instructions old here (tests/test_fwd_cp_loop_budget_cpu.py checks the listing).
+__device__ __forceinline__ float cp_wraw_rot(float I0, float I1, float I2, float Trot) {
+  float acc = I0 * dpp<kB1>(Trot);
+  asm("v_fmac_f32_dpp %0, %1, %2 quad_perm:[2,2,2,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+      "v_fmac_f32_dpp %0, %1, %3 quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+      : "+v"(acc) : "v"(Trot), "v"(I1), "v"(I2));
+  return acc;
+}
+__device__ __forceinline__ double cp_wraw_rot(double I0, double I1, double I2, double Trot) {
+  return mf_fma(I2, dpp<kB0>(Trot), mf_fma(I1, dpp<kB2>(Trot), I0 * dpp<kB1>(Trot)));
+}
+// min(max(v, 0), last), last >= 0: one v_med3_i32 (the compiler forms it for constant bounds only)
+__device__ __forceinline__ int clamp_index(int v, int last) {
+  int r;
+  asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(v), "v"(last));
+  return r;
+}
+}  // namespace cp
+
 // LOSS (default integrator, states only): physics_loss (losses.py:102-127) accumulated while the stamped rows are written
 // (MfRolloutLoss): per lane the squared, time-weighted error of its position component at the <= T2 rows `near` names -- a
 // scalar compare per row, a dozen instructions at a stamped one, its ground truth prefetched one stamp ahead -- then one
@@ -30,6 +59,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
   const int cc = q < 3 ? q : 2;
   const S one = S(1.0), zero = S(0.0);
   const int HW = a.H * a.W, last = HW - 1;
+  int Hv = a.H;                          // in a vector register: the row multiply of the flat cell index then takes its DPP operand itself
+  asm("" : "+v"(Hv));
   const bool has_mu = a.mu != nullptr;   // wave-uniform
   const unsigned moff = a.map_shared ? 0u : (unsigned)b * (unsigned)HW;
   const S* zmap = a.z;
@@ -38,6 +69,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
   // ---- per-lane constants ----
   const bool act = p < a.N;
   const int pi = act ? p : 0;
+  const S den1 = act ? one : (S)__builtin_inff();      // the 1 of the contact sigmoid's denominator; +inf masks an absent point out
   const S P0 = a.points[pi * 3 + 0], P1 = a.points[pi * 3 + 1], P2 = a.points[pi * 3 + 2];
   const int part = act ? a.part[pi] : -1;
   // track speed of this point = tv_v * v + tv_w * w (dphysics.py:75-104, 242-246); 0 for non-driving points
@@ -73,8 +105,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     const S u = M::cell_coord(pc, a.d_max, a.res, a.inv_res);      // lanes 0, 1: ux, uy
     const int ui = (int)M::clamp(u, -lim, lim);                         // trunc toward zero, like .long()
     const S fr = u - (S)ui;
-    const int base = dppi<kB1>(ui) + __mul24(a.H, dppi<kB0>(ui));       // iy + H * ix
-    *idx = min(max(base + cell_off, 0), last);                          // the reference clamps the FLAT index (:432-435)
+    const int base = dppi<kB1>(ui) + __mul24(dppi<kB0>(ui), Hv);        // iy + H * ix
+    *idx = clamp_index(base + cell_off, last);                          // the reference clamps the FLAT index (:432-435)
     const S wa = mf_fma(wa_s, dpp<kB0>(fr), wa_o), wb = mf_fma(wb_s, dpp<kB1>(fr), wb_o);   // exact: 1 - f or f
     *wq = wa * wb;
     if (ou) *ou = u;
@@ -147,8 +179,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
       const Pk2<S> zm = *reinterpret_cast<const Pk2<S>*>(reinterpret_cast<const char*>(a.zmu) + (size_t)((unsigned)idx * 2u * kS));
       g.zc = zm.a; g.mc = zm.b;
     } else {
+      // (friction first: loads return in order, so the wait in front of the height's first use -- the earlier of the two -- covers both)
+      g.mc = ld32(mumap, moff + (unsigned)idx);       // aliases z without a friction map, where nothing reads it
       g.zc = ld32(zmap, moff + (unsigned)idx);
-      g.mc = ld32(mumap, moff + (unsigned)idx);       // aliases z without a friction map; selected after the blend
     }
     g.coln2 = dot3(g0, g0);
     g.il = M::inv_len(g.coln2);
@@ -174,17 +207,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
 #endif
     if (adv) rec_off += rec_step;
   };
-  auto contact = [&](const Geo& g, S vxd, S vw, S tv, S* xdd, S* wd, S* oFr, S* oFf, f4v* rq) {
+  // mu_tag: std::true_type with a friction map, std::false_type without -- launch-constant, so the step loops exist once per value
+  // and the wave picks its copy in front of the loop (a select on has_mu inside was an issue slot per step)
+  auto contact = [&](auto mu_tag, const Geo& g, S vxd, S vw, S tv, S* xdd, S* wd, S* oFr, S* oFf, f4v* rq) {
     const S vp = cp_vel(vxd, vw, g.r);                             // v_p = xd + w x r   (:204)
     const S zq = dot4(g.wq, g.zc);                               // height under the point (:211)
-    const S mub = dot4(g.wq, has_mu ? g.mc : one);             // friction (:216); no map = a map of ones (:562)
+    const S mub = dot4(g.wq, decltype(mu_tag)::value ? g.mc : one);      // friction (:216); no map = a map of ones (:562)
     const S dz = g.zc - dpp<kB0>(g.zc);                           // lane 1: z_f - z_c, lane 2: z_l - z_c
     const S u = mf_fma(dpp<kN12>(dz), n_mul, n_add);                // (-gx, -gy, 1)
     const S inl = M::inv_len(dot3(u, u));
     const S nrm = u * inl;
     const S dh = dpp<kB2>(g.pc) - zq;                             // soft contact + spring-damper along the normal (:220-230)
-    S cj = M::sigmoid_m10(dh);
-    cj = act ? cj : zero;
+    const S cj = M::sigmoid_m10(dh, den1);                        // (an absent point: 1 / (inf + e) = +0)
     const S csum = sum_points(cj);                                // n_contact_pts (:231)
     const S inv_csum = M::div(one, csum);
     const S vn = dot3(vp, nrm);
@@ -195,10 +229,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     const S sn = dot3(s, nrm);
     const S Ff = M::clamp(Nn * cp_tangent(s, sn, nrm), -a.mg, a.mg);   // (:248-251); absent points: cj = 0 -> Fr = Nn = Ff = 0
     const S f = Fr + Ff;
-    const S tau = unrot(cross_pre(g.r, f));                        // r x (Fs + Ff)   (:255)
+    const S tau = cross_pre(g.r, f);                               // r x (Fs + Ff)   (:255), component c in lane (c + 1) % 3
     const S Fsum = sum_points(f), Tsum = sum_points(tau);
     // omega_d = clamp(I^-1 tau)   (:256-257); xdd = (m g ghat + sum F) / m   (:264-266)
-    const S wraw = cp_wraw(I0, I1, I2, Tsum);
+    const S wraw = cp_wraw_rot(I0, I1, I2, Tsum);
     *wd = M::clamp(wraw, -a.omega_max, a.omega_max);
     *xdd = Fsum * a.inv_mass - grav_c;
     *oFr = Fr; *oFf = Ff;
@@ -238,20 +272,34 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     // One step of the two-stream pipeline: geometry `g` / controls (cv, cw) / step size h of step n come in, those of step
     // n + 1 go out into the OTHER buffer set -- the loop below alternates two sets, so nothing is moved between iterations.
     S t_cur = a.T > 1 ? a.ts[1] : zero;
-    const unsigned ctrl_step = (unsigned)a.ctrl_st * kS, v_ctrl_last = v_ctrl + (unsigned)(a.T - 1) * ctrl_step;
-    // the time stamps likewise: a running per-lane byte offset (every lane the same), clamped at the last stamp, and a VECTOR load that
-    // retires with the step's other loads -- the scalar index, address and load it replaces were five issue slots per step
+    const unsigned ctrl_step = (unsigned)a.ctrl_st * kS;
+    // the time stamps likewise: a running per-lane byte offset (every lane the same) and a VECTOR load that retires with the step's
+    // other loads -- the scalar index, address and load it replaces were five issue slots per step
     unsigned v_ts = kS;                                          // stamp n + 1 (t_cur)
     asm("" : "+v"(v_ts));                                        // (a per-lane value the compiler cannot see through)
     const unsigned v_ts_last = (unsigned)max(a.T - 1, 0) * kS;
-    auto ode_step = [&](int n, const Geo& g, Geo& g_next, S cv_n, S cw_n, S h, S& cv_next, S& cw_next, S& h_next) {
-      // next step's controls and step size: loaded before the stores below (vmcnt retires in order)
-      // (vector arithmetic on purpose -- a running per-lane offset clamped at the last row, the previous time stamp carried over:
-      // the scalar index / address chains they replace were 10 scalar instructions per step, each a full issue slot here)
-      v_ctrl = min(v_ctrl + ctrl_step, v_ctrl_last);
+    const char* const pTs = reinterpret_cast<const char*>(a.ts);
+    // next step's controls and step size: loaded in front of the step, before its stores (vmcnt retires in order)
+    // (vector arithmetic on purpose -- running per-lane offsets: the scalar index / address chains they replace were 10 scalar
+    // instructions per step, each a full issue slot here)
+    // Step n reads control row n + 1 <= T - 1: always a row of the rollout.  It reads stamp n + 2, which exists up to step T - 3: the
+    // main loop runs the pairs of steps whose stamps all exist, and the one or two steps behind it clamp the stamp's offset at the
+    // last one (a min per step that the main loop does without).  Per trip of the main loop ONE load brings stamps n + 1 .. n + 3
+    // (so no stamp is carried over the back edge in a register the next load would have to leave alone) and each offset advances
+    // once, by two rows: the second step's control row is read through a base pointer one row on.
+    const Rsrc rCtrl1 = rCtrl + ctrl_step, rCtrl2 = rCtrl1 + ctrl_step;
+    auto next_ctrl = [&](S& cv_next, S& cw_next) {
+      v_ctrl += ctrl_step;
       bload2(rCtrl, v_ctrl, 0u, &cv_next, &cw_next);
+    };
+    auto next_stamp_clamped = [&]() {
       v_ts = min(v_ts + kS, v_ts_last);                        // stamp min(n + 2, T - 1)
-      const S t_next = *reinterpret_cast<const S*>(reinterpret_cast<const char*>(a.ts) + (size_t)v_ts);
+      const S t_next = *reinterpret_cast<const S*>(pTs + (size_t)v_ts);
+      const S h_new = t_next - t_cur;                            // (after the last step: 0, unused)
+      t_cur = t_next;
+      return h_new;
+    };
+    auto ode_step = [&](auto mu_tag, int n, const Geo& g, Geo& g_next, S cv_n, S cw_n, S h, S h_new, S& h_next) __attribute__((always_inline)) {
       const Stamp stamp = loss_peek(n + 1);
       const S tv = cp_track(tv_v, tv_w, cv_n, cw_n);
       // ---- stream B: pose and geometry of step n + 1 (torchdiffeq fixed-grid euler: y_{n+1} = y_n + h f(t_n, y_n)) ----
@@ -266,7 +314,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
       // ---- stream A: contact chain of step n ----
       S xdd, wd, Fr, Ff;
       f4v rq;
-      contact(g, xd, w, tv, &xdd, &wd, &Fr, &Ff, &rq);
+      contact(mu_tag, g, xd, w, tv, &xdd, &wd, &Fr, &Ff, &rq);
       // (measured and not kept: the quad held back and stored a step later next to the row stores -- its last value, the angular
       //  acceleration, only exists where the next step's chain starts -- 0.1662 -> 0.1698 ms at B = 1024; plain instead of
       //  non-temporal stores 0.1662 -> 0.1689; the store itself is ~4 us of the launch, keeping its four values alive ~3)
@@ -275,8 +323,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
       w = mf_fma(h, wd, w);
       oFs = mf_fma(h, Fr, oFs);
       oFf = mf_fma(h, Ff, oFf);
-      h_next = t_next - t_cur;          // (after the last step: 0, unused)
-      t_cur = t_next;
+      h_next = h_new;
       // fused loss: row n + 1 (the pose is already the next one's) -- its wave-uniform branch sits at the very END of the step, so the
       // step's two instruction streams stay in one basic block
       loss_row(x, R2, stamp);
@@ -286,15 +333,34 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
     if (n_steps > 0) gA = geometry(x, R0, R1, R2);
     loss_row(x, R2, loss_peek(0));     // (row 0 = the start state)
     __builtin_amdgcn_s_waitcnt(0);
-    int n = 0;
-    for (; n + 1 < n_steps; n += 2) {
-      ode_step(n, gA, gB, cvA, cwA, hA, cvB, cwB, hB);
-      ode_step(n + 1, gB, gA, cvB, cwB, hB, cvA, cwA, hA);
-    }
-    if (n < n_steps) ode_step(n, gA, gB, cvA, cwA, hA, cvB, cwB, hB);
+    const int n_pairs = a.T >= 4 ? (a.T - 2) >> 1 : 0;      // trips whose steps n, n + 1 are <= T - 3
+    auto run = [&](auto mu_tag) __attribute__((always_inline)) {
+      for (int n = 0; n < 2 * n_pairs; n += 2) {
+        const Pk3<S> tt = *reinterpret_cast<const Pk3<S>*>(pTs + (size_t)v_ts);      // stamps n + 1, n + 2, n + 3
+        bload2(rCtrl1, v_ctrl, 0u, &cvB, &cwB);
+        ode_step(mu_tag, n, gA, gB, cvA, cwA, hA, tt.b - tt.a, hB);
+        bload2(rCtrl2, v_ctrl, 0u, &cvA, &cwA);
+        v_ctrl += 2u * ctrl_step;
+        v_ts += 2u * kS;
+        t_cur = tt.c;
+        ode_step(mu_tag, n + 1, gB, gA, cvB, cwB, hB, tt.c - tt.b, hA);
+      }
+      const int n = 2 * n_pairs;
+      if (n < n_steps) {
+        const S h_a = next_stamp_clamped();
+        next_ctrl(cvB, cwB);
+        ode_step(mu_tag, n, gA, gB, cvA, cwA, hA, h_a, hB);
+        if (n + 1 < n_steps) {
+          const S h_b = next_stamp_clamped();
+          next_ctrl(cvA, cwA);
+          ode_step(mu_tag, n + 1, gB, gA, cvB, cwB, hB, h_b, hA);
+        }
+      }
+    };
+    if (has_mu) run(std::true_type{}); else run(std::false_type{});
   } else {
     __builtin_amdgcn_s_waitcnt(0);
-    for (int n = 0; n < n_steps; ++n) {
+    auto dyn_step = [&](auto mu_tag, int n) __attribute__((always_inline)) {
       // next step's controls: loaded before the stores below (vmcnt retires in order)
       const int nn = min(n + 1, a.T - 1);
       S cv_next, cw_next;
@@ -305,7 +371,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
       const Geo g = geometry(x, R0, R1, R2);
       emit_row(x, xd, w, R0, R1, R2, n > 0 ? 1u : 0u);      // n = 0: the initial state as a placeholder in row 0, overwritten one iteration later
       f4v rq;
-      contact(g, xd, w, tv, &xdd, &wd, &Fr, &Ff, &rq);
+      contact(mu_tag, g, xd, w, tv, &xdd, &wd, &Fr, &Ff, &rq);
       if constexpr (REC) rec_store(rq, 1u);
       // update_state (:274-288): xd += xdd h ; x += xd_new h ; w += wd h ; R <- R (I + K sin + K^2 (1 - cos))
       const S h = a.dt;
@@ -333,7 +399,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))
       R0 = n0; R1 = n1; R2 = n2;
       oFs = Fr; oFf = Ff;                                               // true forces of this step
       cv = cv_next; cw = cw_next;
-    }
+    };
+    if (has_mu) { for (int n = 0; n < n_steps; ++n) dyn_step(std::true_type{}, n); }
+    else { for (int n = 0; n < n_steps; ++n) dyn_step(std::false_type{}, n); }
   }
   if (n_steps > 0 || INTEG == MF_INTEG_ODEINT_EULER) emit_row(x, xd, w, R0, R1, R2, 1u);
   if constexpr (LOSS) {

@@ -76,6 +76,9 @@ struct Mth {
   static __device__ __forceinline__ S cell_coord(S q, S d_max, S res, S) { return (q + d_max) / res; }
   static __device__ __forceinline__ S sqrt(S v) { return mf_sqrt(v); }
   static __device__ __forceinline__ S sigmoid_m10(S dh) { return (S)1 / ((S)1 + mf_exp((S)10 * dh)); }
+  // the same with the 1 of the denominator handed in: 1 gives sigmoid_m10(dh) bit for bit, +inf gives +0 (a lane that masks its
+  // point out holds +inf there and spends no instruction on the mask)
+  static __device__ __forceinline__ S sigmoid_m10(S dh, S den1) { return (S)1 / (den1 + mf_exp((S)10 * dh)); }
   // v / max(|v|, eps) given |v|^2
   static __device__ __forceinline__ S inv_len(S len2) { return (S)1 / mf_max(mf_sqrt(len2), (S)1e-6); }
   static __device__ __forceinline__ S len_of(S len2, S) { return mf_sqrt(len2); }      // |v| given |v|^2 (and inv_len(|v|^2), unused here)
@@ -101,6 +104,9 @@ struct Mth<float, true> {
   static __device__ __forceinline__ float sqrt(float v) { return __builtin_amdgcn_sqrtf(v); }
   static __device__ __forceinline__ float sigmoid_m10(float dh) {
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(14.426950408889634f * dh));  // exp(10 dh) = 2^(10 log2(e) dh)
+  }
+  static __device__ __forceinline__ float sigmoid_m10(float dh, float den1) {      // den1 = 1: as above; +inf: +0 (v_rcp_f32 of +inf)
+    return __builtin_amdgcn_rcpf(den1 + __builtin_amdgcn_exp2f(14.426950408889634f * dh));
   }
   static __device__ __forceinline__ float inv_len(float len2) { return __builtin_amdgcn_rsqf(fmaxf(len2, 1e-12f)); }
   // |v| = |v|^2 / |v| from the reciprocal at hand: a multiply instead of a second transcendental (below the 1e-6 floor of inv_len
