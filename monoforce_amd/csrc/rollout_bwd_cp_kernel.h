@@ -681,8 +681,15 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         if constexpr (!XS_ONLY) { og_xds -= sg_xds; og_om -= sg_om; og_r -= sg_r; og_fs -= sg_fs; og_ff -= sg_ff; }
       };
       constexpr int kSlots = SLOTS, kPlanesD = ODE ? 0 : 6, kPlanes = (XS_ONLY ? 10 : 12) + kPlanesD;      // dynamics(): six more (struct CoefD)
-      constexpr bool kPow2 = (kSlots & (kSlots - 1)) == 0;
       __shared__ f4v ring[kSlots * kPlanes * 64];
+      // float: a wave's place in the ring runs as its lanes' BYTE offset (slot, lane), stepped by whole slots and wrapped by an unsigned
+      // minimum (off - ring size is huge below the ring's end): no multiply by the slot size and no shift per access, a slot's planes
+      // and the slots next to it are immediate offsets.  double (the validation build, at its register limit) keeps slot numbers and the
+      // loop forms that go with them: kRunning selects, as the cp_* overloads do for the arithmetic.
+      constexpr bool kRunning = std::is_same<S, float>::value;
+      constexpr unsigned kSlotBytes = (unsigned)(kPlanes * 64 * sizeof(f4v)), kRingBytes = (unsigned)kSlots * kSlotBytes;
+      auto ring_wrap = [](unsigned off) { return min(off, off - kRingBytes); };      // off < 2 ring sizes
+      auto ring_at = [&](unsigned off) { return reinterpret_cast<f4v*>(reinterpret_cast<char*>(ring) + off); };
       __shared__ int flags[4];      // steps written, steps read (HANDOFF: steps answered); loss-value shares in l_part (fused loss value); the snap's cell in snap_c
       typedef __attribute__((address_space(3))) volatile int LdsCounter;      // (a generic volatile pointer would make FLAT accesses)
       LdsCounter* vflags = (LdsCounter*)flags;
@@ -875,7 +882,7 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         // the computing wave found the ring empty in 82 of 248 step pairs instead of 2: profiles/stream_scatter_ab.txt.)
         [[maybe_unused]] unsigned pend_idx = 0u;      // "cell 0, answer (0, 0)": absorbed without a flush
         [[maybe_unused]] S pend_z = zero, pend_m = zero;
-        auto put = [&](const Slot& r, unsigned slot, int o) {
+        auto put = [&](const Slot& r, unsigned off, int o) {      // off: the slot's place -- this lane's byte offset (kRunning) or the slot's number
             Rec k;
             rebuild(r.st, r.sv, k);
             if constexpr (HANDOFF) {
@@ -936,7 +943,7 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
               d5 = f4v{dpp<kB2>(m1), dpp<kB2>(m2), dpp<kB2>(m0), zero};  // M[2][0], M[2][1], M[2][2]
             }
             room(o + 1);
-            f4v* out = ring + slot * (unsigned)(kPlanes * 64) + lane;
+            f4v* out = kRunning ? ring_at(off) : ring + off * (unsigned)(kPlanes * 64) + lane;
             [[maybe_unused]] f2v old_ans = {zero, zero};      // (HANDOFF only)
             [[maybe_unused]] S old_idx = zero;
             if constexpr (HANDOFF) {      // step o - kSlots (stream_ring::answer_in_slot), this wave's own: its cell and its answer, before they are overwritten
@@ -960,7 +967,9 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
 #endif
           };
         int ord = BATCH * fk;                       // ordinal of the first step of this wave's next batch to WRITE
-        unsigned sbase = kB * (unsigned)fk;         // ... and its ring slot: (BATCH j) mod kSlots
+        // ... and its ring slot, (BATCH j) mod kSlots: this lane's byte offset (kRunning) or the slot's number
+        constexpr unsigned kStep = kRunning ? kSlotBytes : 1u;      // one slot on, in that unit
+        unsigned wbase = kRunning ? kB * (unsigned)fk * kSlotBytes + (unsigned)lane * (unsigned)sizeof(f4v) : kB * (unsigned)fk;
         auto fetch3 = [&](Slot (&s)[BATCH]) {
 #pragma unroll
           for (int i = 0; i < BATCH; ++i) fetch(s[i]);
@@ -977,10 +986,13 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         auto put3 = [&](const Slot (&s)[BATCH]) {
           pub = ord;
 #pragma unroll
-          for (int i = 0; i < BATCH; ++i) put(s[i], sbase + (unsigned)i, ord + i);
+          for (int i = 0; i < BATCH; ++i) put(s[i], wbase + (unsigned)i * kStep, ord + i);
           publish(ord + BATCH);
           ord += 2 * BATCH;
-          if constexpr (kSlots != 2 * BATCH) sbase = sbase + 2u * kB >= (unsigned)kSlots ? sbase + 2u * kB - (unsigned)kSlots : sbase + 2u * kB;
+          if constexpr (kSlots != 2 * BATCH) {
+            if constexpr (kRunning) wbase = ring_wrap(wbase + 2u * kB * kSlotBytes);
+            else wbase = wbase + 2u * kB >= (unsigned)kSlots ? wbase + 2u * kB - (unsigned)kSlots : wbase + 2u * kB;
+          }
         };
         Slot A[BATCH], B[BATCH], C[BATCH];
         const int n_full = (n + 1) / BATCH;         // whole batches of BATCH steps in the launch (n + 1 steps)
@@ -1002,7 +1014,7 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         // the last one or two steps: the wave whose turn it would be (its offsets stand on them, its half of the ring is next)
         if (fk == (n_full & 1)) {
           int o = BATCH * n_full;
-          unsigned sl = sbase;
+          unsigned sl = wbase;
           while (m >= 0) {                          // (fetch moves m)
             Slot r0;
             fetch(r0);
@@ -1010,7 +1022,7 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
             pub = o;
             put(r0, sl, o);
             publish(o + 1);
-            ++sl; ++o;
+            sl += kStep; ++o;      // (inside a batch's slots: no wrap)
           }
         }
         MF_PROF_ADD(2 + 4 * fk, t_fetcher);
@@ -1044,7 +1056,10 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
       }
         // ---------------- the computing wave ----------------
         int consumed = 0, seen = 0;                   // records read so far; the fetching wave's counter as last read
-        unsigned rslot = 0u;                          // ring slot read next (running, wraps at kSlots)
+        // The ring slot read last, as this lane's byte offset into the ring (running; starts one slot in front of slot 0).  The planes of a
+        // slot are immediate offsets of its reads, and so is the stride to the first slot of a trip -- see `grab`.
+        unsigned rlast = (unsigned)(kSlots - 1) * kSlotBytes + (unsigned)lane * (unsigned)sizeof(f4v);
+        unsigned rslot = 0u;                          // (!kRunning: the ring slot read next, wraps at kSlots)
         UpIn uZ;                                      // the upstream gradient of output row 0 (the initial state): not in the ring
         load_upstream(0, uZ);
         S l_row0 = zero;                          // row 0's term of the loss value (the other rows' are the fetching waves')
@@ -1066,7 +1081,7 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           S vp, inlr, wq, zc, mcv, wsb, wsa;      // -(1 / |u|) / res; d wq / d(fx, fy) / res
           S e, il, eci;                     // gate_col0 e / |col0|
           int idx;
-          unsigned off;                     // HANDOFF: the step's place in the ring (elements), where its answer goes
+          unsigned off;                     // HANDOFF: the step's place in the ring (this lane's byte offset), where its answer goes
           // dynamics() only (struct "CoefD", six more planes): the adjoint-independent half of the Rodrigues step's backward
           S wn, kv, q0, q1, q2, Rk, kk, sn_, oc, cga, cgb, idn, idn2, ith;      // cga = h (1 - cos), cgb = h sin
           S M00, M01, M02, M10, M11, M12, M20, M21, M22;                      // M[m][j], every lane holds all nine
@@ -1091,10 +1106,22 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           n_waited += __builtin_amdgcn_readfirstlane(seen) < consumed + k ? 1u : 0u;
 #endif
         };
-        auto grab = [&](Coef& c, UpIn& up) {          // the next step out of the ring (it is there: ensure)
-          c.off = (kPow2 ? (unsigned)(consumed & (kSlots - 1)) : rslot) * (unsigned)(kPlanes * 64) + (unsigned)lane;
-          const f4v* o = ring + c.off;
-          if constexpr (!kPow2) rslot = rslot + 1u == (unsigned)kSlots ? 0u : rslot + 1u;
+        // The next step out of the ring (it is there: ensure).  `ahead`: 1 = the slot behind the one read last, 2 = the one behind that
+        // (the second step of a trip; the running offset moves once per trip, by both).  The loop's trips start on an odd slot -- one step
+        // is taken in front of the loop -- and the number of slots is even, so a trip's FIRST step never wraps (`first_of_pair`).
+        static_assert(kSlots % 2 == 0, "a trip's first step must not be the ring's last slot plus one");
+        auto grab = [&](Coef& c, UpIn& up, auto ahead, auto first_of_pair) {
+          constexpr unsigned kAhead = (unsigned)decltype(ahead)::value;
+          const f4v* o;
+          if constexpr (!kRunning) {
+            c.off = rslot * (unsigned)(kPlanes * 64) + (unsigned)lane;      // (elements)
+            o = ring + c.off;
+            rslot = rslot + 1u == (unsigned)kSlots ? 0u : rslot + 1u;
+          } else {
+            if constexpr (decltype(first_of_pair)::value) c.off = rlast + kSlotBytes;
+            else { c.off = ring_wrap(rlast + kAhead * kSlotBytes); rlast = c.off; }
+            o = ring_at(c.off);
+          }
           const f4v c0 = o[0], c1 = o[64], c2 = o[128], c3 = o[192], c4 = o[256], c5 = o[320], c6 = o[384], c7 = o[448], c8 = o[512], c9 = o[576];
           const S idx_bits = c7.w;       // (__builtin_bit_cast applied to the element expression itself reads element 0 of the vector)
           c.R0 = c0.x; c.R1 = c0.y; c.R2 = c0.z; c.h = c0.w;
@@ -1131,7 +1158,7 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           vflags[1] = consumed;                        // (LDS runs a wave's operations in order: the reads of grab are done by then)
         };
         auto take = [&](Coef& c, UpIn& up) {
-          ensure(1); grab(c, up);
+          ensure(1); grab(c, up, std::integral_constant<int, 1>{}, std::false_type{});
           if constexpr (HANDOFF) seen = vflags[0]; else release();
         };
         auto answered = [&](int k) {                  // HANDOFF: the first k steps' answers are in their slots (LDS runs a wave's operations in order)
@@ -1151,11 +1178,22 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           gxdd = h * sum_points(lxd); gwd = h * sum_points(lw);
           lxd = mf_fma(h, lx, lxd);
           const S g0 = h * lR0, g1 = h * lR1, g2 = h * lR2;
-          const S g01 = dpp<kRot1>(g0), g02 = dpp<kRot2>(g0), g11 = dpp<kRot1>(g1), g12 = dpp<kRot2>(g1), g21 = dpp<kRot1>(g2), g22 = dpp<kRot2>(g2);
-          lw += (dpp<kRot1>(c.R0) * g02 - dpp<kRot2>(c.R0) * g01) + (dpp<kRot1>(c.R1) * g12 - dpp<kRot2>(c.R1) * g11) + (dpp<kRot1>(c.R2) * g22 - dpp<kRot2>(c.R2) * g21);
-          lR0 += g01 * c.w2 - g02 * c.w1;
-          lR1 += g11 * c.w2 - g12 * c.w1;
-          lR2 += g21 * c.w2 - g22 * c.w1;
+          if constexpr (kRunning) {      // (cross-lane operands inside the arithmetic, rollout_cp_common.h: no rotated copies of g or R in registers of their own)
+            S dw0, dw1, dw2, u0, u1, u2;
+            cp_rot_back(g0, c.R0, c.w1, c.w2, &dw0, &u0);
+            cp_rot_back(g1, c.R1, c.w1, c.w2, &dw1, &u1);
+            cp_rot_back(g2, c.R2, c.w1, c.w2, &dw2, &u2);
+            lw += dpp<kRot1>((dw0 + dw1) + dw2);      // (the three terms are formed rotated, as cross_pre leaves them: home in this operand)
+            lR0 += u0;
+            lR1 += u1;
+            lR2 += u2;
+          } else {
+            const S g01 = dpp<kRot1>(g0), g02 = dpp<kRot2>(g0), g11 = dpp<kRot1>(g1), g12 = dpp<kRot2>(g1), g21 = dpp<kRot1>(g2), g22 = dpp<kRot2>(g2);
+            lw += (dpp<kRot1>(c.R0) * g02 - dpp<kRot2>(c.R0) * g01) + (dpp<kRot1>(c.R1) * g12 - dpp<kRot2>(c.R1) * g11) + (dpp<kRot1>(c.R2) * g22 - dpp<kRot2>(c.R2) * g21);
+            lR0 += g01 * c.w2 - g02 * c.w1;
+            lR1 += g11 * c.w2 - g12 * c.w1;
+            lR2 += g21 * c.w2 - g22 * c.w1;
+          }
           } else {
             // dynamics(): the adjoint of  xd' = xd + xdd h, x' = x + xd' h, w' = w + wd h, R' = R M(w')  on the fetching waves'
             // coefficients (the derivation: `vjp` above); the forces of this step are outputs themselves
@@ -1184,10 +1222,17 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           }
           // ---- RHS backward ----
           const S mwd = c.mw * gwd;
-          const S gtau = J0 * dpp<kB0>(mwd) + J1 * dpp<kB1>(mwd) + J2 * dpp<kB2>(mwd);      // I^-T m
-          const S gt1 = dpp<kRot1>(gtau), gt2 = dpp<kRot2>(gtau);
-          const S gq = mf_fma(gxdd, a.inv_mass, gt1 * c.r2 - gt2 * c.r1);      // to both force outputs: sum + (tau += r x f)
-          S gr = c.f1 * gt2 - c.f2 * gt1;
+          S gq, gr;      // gq: to both force outputs, sum + (tau += r x f); gt1, gt2 below: the rotations of gtau = I^-T m
+          if constexpr (kRunning) {
+            S gtr;                                      // gt1 r2 - gt2 r1;  gr = f1 gt2 - f2 gt1
+            cp_cross_pair(cp_colT(J0, J1, J2, mwd), c.r2, c.r1, c.f2, c.f1, &gtr, &gr);
+            gq = mf_fma(gxdd, a.inv_mass, gtr);
+          } else {
+            const S gtau = J0 * dpp<kB0>(mwd) + J1 * dpp<kB1>(mwd) + J2 * dpp<kB2>(mwd);
+            const S gt1 = dpp<kRot1>(gtau), gt2 = dpp<kRot2>(gtau);
+            gq = mf_fma(gxdd, a.inv_mass, gt1 * c.r2 - gt2 * c.r1);
+            gr = c.f1 * gt2 - c.f2 * gt1;
+          }
           S gFr = gFr_up + gq;
           const S gFf_ = gFf_up + gq;
           const S gNn = dot3(gFf_, c.stvG);
@@ -1217,11 +1262,18 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           // the terrain / friction gradient of the footprint cell: n = u / |u|, u = (-gx, -gy, 1)
           const S dotn = dot3(gn, c.nrm);
           const S gg = (gn - dotn * c.nrm) * c.inlr;                // lane 0: ggx, lane 1: ggy
-          const S ggp = dpp<0x51>(gg);                               // quad_perm [1,0,1,1]
-          const S nz = mf_fma(gzq, c.wq, cgA * gg + cgB * ggp);
-          const S nm = gmuq * c.wq;
+          S nz, nm;
+          if constexpr (kRunning) {
+            S gcell;                                                 // cgA gg + cgB quad_perm[1,0,1,1](gg);  nm = gmuq wq
+            cp_cell_terms(cgA, cgB, gg, gmuq, c.wq, &gcell, &nm);
+            nz = mf_fma(gzq, c.wq, gcell);
+          } else {
+            const S ggp = dpp<0x51>(gg);                             // quad_perm [1,0,1,1]
+            nz = mf_fma(gzq, c.wq, cgA * gg + cgB * ggp);
+            nm = gmuq * c.wq;
+          }
           if constexpr (HANDOFF) {      // back to the fetching wave that owns the slot: one 8-byte LDS store
-            *reinterpret_cast<f2v*>(ring + c.off + kAnsPlane) = f2v{nz, nm};
+            *reinterpret_cast<f2v*>(ring_at(c.off) + kAnsPlane) = f2v{nz, nm};
           } else {   // this lane's cell accumulator
             const unsigned ni = (unsigned)c.idx;
             const bool same = !act | (ni == acc_idx);            // absent points contribute exact zeros: never flushed
@@ -1234,9 +1286,16 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           const S vq = gzq * c.zc + gmuq * c.mcv;
           const S gpx = dot4(vq, c.wsb), gpy = dot4(vq, c.wsa);
           const S gp = mask_or(mask_or(mask_or(zero, gpx, lane0), gpy, lane1), gdh, lane2);
-          const S gvp1 = dpp<kRot1>(gvp), gvp2 = dpp<kRot2>(gvp);
-          gr += gvp1 * c.w2 - gvp2 * c.w1;                       // dr += gvp x w
-          const S gw_p = c.r1 * gvp2 - c.r2 * gvp1;          // dw += r x gvp
+          S gw_p;                                                // dr += gvp x w;  dw += r x gvp
+          if constexpr (kRunning) {
+            S gvw;
+            cp_cross_pair(gvp, c.w2, c.w1, c.r2, c.r1, &gvw, &gw_p);
+            gr += gvw;
+          } else {
+            const S gvp1 = dpp<kRot1>(gvp), gvp2 = dpp<kRot2>(gvp);
+            gr += gvp1 * c.w2 - gvp2 * c.w1;
+            gw_p = c.r1 * gvp2 - c.r2 * gvp1;
+          }
           const S qa = gp + gr;
           lx += gp; lxd += gvp; lw += gw_p;
           lR0 = mf_fma(qa, P0, lR0); lR1 = mf_fma(qa, P1, lR1); lR2 = mf_fma(qa, P2, lR2);
@@ -1247,9 +1306,9 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
         };
         auto crunch = [&](int n, const Coef& c, const UpIn& up, Coef& c_next, UpIn& up_next, auto more, auto paired) {
           add_upstream_masked(up);
-          if constexpr (decltype(paired)::value == 1) grab(c_next, up_next);                     // first of a pair: ensured by the loop
+          if constexpr (decltype(paired)::value == 1) grab(c_next, up_next, std::integral_constant<int, 1>{}, std::integral_constant<bool, kRunning>{});      // first of a pair: ensured by the loop
           else if constexpr (decltype(paired)::value == 2) {                                     // second of a pair
-            grab(c_next, up_next);
+            grab(c_next, up_next, std::integral_constant<int, kRunning ? 2 : 1>{}, std::false_type{});      // (!kRunning: one form of grab)
             if constexpr (HANDOFF) seen = vflags[0]; else release();
           } else if constexpr (decltype(more)::value) take(c_next, up_next);
           if constexpr (!HANDOFF) flush_stash();
@@ -1262,7 +1321,9 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           chain(n, c, up);
 #endif
           // HANDOFF: a trip's two answers are counted at once (ordinal of step n: n_steps - 1 - n)
-          if constexpr (HANDOFF && decltype(paired)::value != 1) answered(n_steps - n);
+          // (in a trip both steps have been grabbed by now: n_steps - n == consumed - 1, and `consumed` is the counter the loop runs on)
+          if constexpr (HANDOFF && kRunning && decltype(paired)::value == 2) answered(consumed - 1);
+          else if constexpr (HANDOFF && decltype(paired)::value != 1) answered(n_steps - n);
         };
         using std::true_type;
         using std::false_type;
@@ -1271,10 +1332,24 @@ rollout_bwd_cp_kernel(const RolloutBwdArgs<S> a) {
           take(cA, uA);
           MF_PROF_ADD(3, t_k0); MF_PROF_OUT(19, acc_wait);
           using single = std::integral_constant<int, 0>;
-          for (; n >= 2; n -= 2) {
-            ensure(2);
-            crunch(n, cA, uA, cB, uB, true_type{}, std::integral_constant<int, 1>{});
-            crunch(n - 1, cB, uB, cA, uA, true_type{}, std::integral_constant<int, 2>{});
+          // (this wave's loads -- per-lane constants, row 0's upstream -- have all been issued: waited for HERE, once; left pending they
+          //  cost the loop a wait instruction in front of each first use, trip after trip, because the loop's entry is one of its predecessors)
+          if constexpr (kRunning) {
+            __builtin_amdgcn_s_waitcnt(0);
+            // (one counter: n == n_steps - consumed at the top of a trip)
+            while (n_steps - consumed >= 2) {
+              const int nn = n_steps - consumed;
+              ensure(2);
+              crunch(nn, cA, uA, cB, uB, true_type{}, std::integral_constant<int, 1>{});
+              crunch(nn - 1, cB, uB, cA, uA, true_type{}, std::integral_constant<int, 2>{});
+            }
+            n = n_steps - consumed;
+          } else {
+            for (; n >= 2; n -= 2) {
+              ensure(2);
+              crunch(n, cA, uA, cB, uB, true_type{}, std::integral_constant<int, 1>{});
+              crunch(n - 1, cB, uB, cA, uA, true_type{}, std::integral_constant<int, 2>{});
+            }
           }
           if (n == 1) { crunch(1, cA, uA, cB, uB, true_type{}, single{}); crunch(0, cB, uB, cA, uA, false_type{}, single{}); }
           else crunch(0, cA, uA, cB, uB, false_type{}, single{});

@@ -83,6 +83,75 @@ __device__ __forceinline__ S cross_pre(S a, S b) {
 template <typename S>
 __device__ __forceinline__ S unrot(S d) { return dpp<kRot1>(d); }
 
+// ---- the streaming backward's adjoint chain: cross-lane operands INSIDE the arithmetic instruction (float) ---------------------
+// The computing wave of the streaming backward (rollout_bwd_cp_kernel.h, `chain`) runs alone on its SIMD, and a v_mov_b32_dpp that only
+// brings a rotated or broadcast copy into a register of its own is one more instruction on the adjoint chain's dependent path (what
+// that is worth was measured: DESIGN.md section 8 -- about two cycles per instruction removed, not an issue slot's four).  The compiler
+// folds such a move into the ONE instruction that uses it when that is a VOP2 whose result is not tied to an operand; it leaves it in
+// front of a fused multiply-add and in front of two users.  The float forms below write those as  multiply (the compiler's own, its
+// DPP operand negated where the product is subtracted: exact), then v_fmac_f32 with the cross-lane value as its DPP src0  -- the
+// multiplies and fused multiply-adds of a group are the ones the plain expressions compile to, on the same operands in the same order.
+// (Checked on the listing of the fit step's kernel, instruction by instruction; what the compiler makes of the adds AROUND a group --
+// `gr += ...`, the sum of the three rotated terms -- is its own choice in either form.)  float only: the float64 validation build keeps
+// the plain expressions in `chain` itself.
+// The two wait states a DPP read of a fresh VALU result needs are invisible to the compiler inside assembly text.  Each form says
+// why its DPP operand is old enough: a compiler instruction that reads the SAME register through DPP (and is padded by the compiler)
+// feeds the statement's accumulator, or the statement holds the distance itself.  NOTHING IN THE SOURCE ENFORCES the first kind: it
+// holds as long as the compiler puts no copy of that register (a v_mov, a v_accvgpr_read, a spill reload -- these kernels use AGPRs)
+// between its own DPP read and the statement and hands the statement the copy.  tests/test_bwd_stream_loop_budget_cpu.py walks the
+// listing the installed compiler produces, for every streaming kernel; if that walk ever fails, the remedy is cp_colT's pattern: the
+// distance inside the statement (an `s_nop 1` in front of the first DPP read), at one issue slot per group.
+// One statement per group, not volatile (see cp_wraw_rot in rollout_fwd_cp_kernel.h).
+#define MF_DPP_QP(a, b, c, d) " quad_perm:[" #a "," #b "," #c "," #d "] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+#define MF_DPP_ROT1 MF_DPP_QP(1, 2, 0, 0)
+#define MF_DPP_ROT2 MF_DPP_QP(2, 0, 1, 1)
+// The adjoint of r = R P through g = h lR (row i of R in the ring, this lane's column):
+//   *d : (R_i x g)-term of lw,  Rot1(R) Rot2(g) - Rot2(R) Rot1(g), left ROTATED (component c in lane (c + 1) % 3, as cross_pre leaves it:
+//        R g' - R' g with ' = Rot1) -- the caller adds the three rows' terms and brings the sum home with one DPP operand (Rot1)
+//   *u : Rot1(g) w2 - Rot2(g) w1, the term of lR_i (w1, w2: the rotated copies of w the ring carries)
+// g is old enough: the product that starts *u reads it through DPP and the statement reads *u.
+__device__ __forceinline__ void cp_rot_back(float g, float R, float w1, float w2, float* d, float* u) {
+  float t = -dpp<kRot1>(R) * g, v = -dpp<kRot2>(g) * w1;
+  asm("v_fmac_f32_dpp %0, %2, %3" MF_DPP_ROT1 "\n\t"
+      "v_fmac_f32_dpp %1, %2, %4" MF_DPP_ROT1
+      : "+v"(t), "+v"(v) : "v"(g), "v"(R), "v"(w2));
+  *d = t; *u = v;
+}
+// J^T m with column c of J in this lane (J0, J1, J2) and m's components in the quad's lanes:  J0 m_0 + J1 m_1 + J2 m_2, summed in the order
+// the plain expression contracts to -- fma(J2, m_2, fma(J0, m_0, J1 m_1)).  m is old enough (the first product reads it through DPP); the
+// RESULT is read through DPP by what follows (cp_cross_pair), and the compiler does not pad a DPP read of a register that assembly text
+// wrote: the two wait states close the statement.
+__device__ __forceinline__ float cp_colT(float J0, float J1, float J2, float m) {
+  float acc = J1 * dpp<kB1>(m);
+  asm("v_fmac_f32_dpp %0, %1, %2" MF_DPP_QP(0, 0, 0, 0) "\n\t"
+      "v_fmac_f32_dpp %0, %1, %3" MF_DPP_QP(2, 2, 2, 2) "\n\t"
+      "s_nop 1"
+      : "+v"(acc) : "v"(m), "v"(J0), "v"(J2));
+  return acc;
+}
+// Both cross products a vector v (components in the lanes) enters, against operands that arrive rotated:
+//   *x = Rot1(v) a1 - Rot2(v) a2        *y = b2 Rot2(v) - b1 Rot1(v)
+// v is old enough: both leading products read it through DPP and the statement reads both.
+__device__ __forceinline__ void cp_cross_pair(float v, float a1, float a2, float b1, float b2, float* x, float* y) {
+  float p = -dpp<kRot2>(v) * a2, r = -dpp<kRot1>(v) * b1;
+  asm("v_fmac_f32_dpp %0, %2, %3" MF_DPP_ROT1 "\n\t"
+      "v_fmac_f32_dpp %1, %2, %4" MF_DPP_ROT2
+      : "+v"(p), "+v"(r) : "v"(v), "v"(a1), "v"(b2));
+  *x = p; *y = r;
+}
+// The footprint cell's share of the normal's finite differences and the friction product of a step's answer:
+//   *t = cgA gg + cgB swap(gg)   (swap = quad_perm [1,0,1,1]: lane 0 <-> 1)        *nm = gmuq wq
+// gg is fresh when the statement begins; the two plain products in front of the DPP read are the two wait states (neither writes gg:
+// both results are early-clobber).
+__device__ __forceinline__ void cp_cell_terms(float cgA, float cgB, float gg, float gmuq, float wq, float* t, float* nm) {
+  float a, b;
+  asm("v_mul_f32 %0, %2, %3\n\t"
+      "v_mul_f32 %1, %5, %6\n\t"
+      "v_fmac_f32_dpp %0, %3, %4" MF_DPP_QP(1, 0, 1, 1)
+      : "=&v"(a), "=&v"(b) : "v"(cgA), "v"(gg), "v"(cgB), "v"(gmuq), "v"(wq));
+  *t = a; *nm = b;
+}
+
 // ---- the contact model's formulas, ONE definition for the forward and the backward -------------------------------------------
 // The backward rebuilds a step's intermediates from the saved state rows (and, where the forward kept one, from its compact
 // per-step record).  Autograd differentiates the function the forward EVALUATED -- its clamp decisions, the sign of the normal

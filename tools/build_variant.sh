@@ -17,7 +17,8 @@ done
 for tu in "$@"; do
   b=$(basename "$tu" .hip)
   contract="-ffp-contract=off"; case "$b" in *_fast|*_cost) contract="-ffp-contract=fast-honor-pragmas";; esac
-  extra=""; [ "$b" = rollout_bwd_dyn_cp_fast ] && extra="-mllvm -amdgpu-sched-strategy=max-ilp"
+  # (the Makefile's per-unit scheduling strategy)
+  extra=""; case "$b" in rollout_bwd_dyn_cp_fast|rollout_bwd_cp_stream_fast) extra="-mllvm -amdgpu-sched-strategy=max-ilp";; esac
   (cd "$src" && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -fno-slp-vectorize $contract $extra $flags -Wall -Wno-unused-variable -c "$b.hip" -o /tmp/mf_variant_$name/$b.o 2>&1 | grep -E "error|undefined" ) &
   objs="$objs /tmp/mf_variant_$name/$b.o"
 done
