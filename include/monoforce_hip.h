@@ -542,6 +542,54 @@ typedef struct MfHeightmapDesc {
 int mf_estimate_heightmap_f32(const MfHeightmapDesc* desc, const float* points, const float* x_bins, const float* y_bins,
                               int32_t* scratch, float* hm, void* hip_stream);
 
+/* ---- Rigid-terrain label maps (datasets/rough.py:621-649 with :343-365 and :545-601) for S samples at once -------------------------------
+ * What the reference builds per sample on the host -- the cloud projected into every camera's segmentation mask, the points with a rigid
+ * label gravity-aligned, the robot's footprint swept along the recorded poses, estimate_heightmap of both -- as one launch sequence.
+ * Inputs, all device pointers.  points [n_points][3] float32: the clouds of the S samples one after the other; offsets [S+1] int32: sample s
+ *   owns the rows offsets[s] .. offsets[s+1]-1 (N_s of them, possibly none; the range is clamped into [0, n_points]).  seg [S][C][Hi][Wi]
+ *   uint8: the label masks.  rots [S][C][3][3], trans [S][C][3], intrins [S][C][3][3] float32: camera c of sample s starts at
+ *   s * *_stride_s + c * 9 (3 for trans) elements; a stride of 0 shares one set of cameras among the samples.  pose_align [S][3][4] float64:
+ *   the gravity alignment of the sample's cloud.  poses [S][T][3][4] float64: the recorded poses, already aligned (T may be 0).  fx [Fx],
+ *   fy [Fy] float32: the footprint's coordinates.  x_bins, y_bins [n] float32: the bin edges of estimate_heightmap, torch.arange(-d_max,
+ *   d_max, grid_res).  scratch: S*n*n int32, initialised by the call.
+ * Items.  Sample s has N_s + T*Fx*Fy items: its cloud points, then its footprint points.
+ * Cloud point p, for each camera c with rotation R, translation t, intrinsics K -- float32, every operation rounded on its own, in this
+ *   order (the translation unit is built with -ffp-contract=off and IEEE division):
+ *     p' = p - t;   q_i = (R[0][i] p'_x + R[1][i] p'_y) + R[2][i] p'_z   (R^T p');   w_i = (K[i][0] q_0 + K[i][1] q_1) + K[i][2] q_2;
+ *     u = w_0 / w_2,  v = w_1 / w_2;   the camera SEES p iff  w_2 > 0 && u > 1 && u < Wi-1 && v > 1 && v < Hi-1  (false when anything is
+ *     NaN; utils.py:38-43);  its label is seg[s][c][(int)v][(int)u] (truncation).
+ *   p is KEPT iff some camera sees it with a label l in the class set: bit (l & 31) of class_set[l >> 5].  A row with a NaN is never kept.
+ *   A kept point becomes g = pose_align[s] . p in float64, per row ((r0 x + r1 y) + r2 z) + t, each component then rounded to float32.
+ * Footprint point (t, j, i), item index (t * Fy + j) * Fx + i: in float64, g = poses[s][t] . (fx[i], fy[j], 0) by the same row formula,
+ *   where the z row's translation is first reduced by |clearance|; then rounded to float32.  It is not aligned again.
+ * Every g then passes estimate_heightmap's filters, bin search and per-cell maximum exactly (MfHeightmapDesc above): rows with a NaN,
+ *   points within r_min of the origin in xy (r_min < 0: no such filter) and points outside the open box (-d_max, d_max)^2 x (h_min, h_max)
+ *   are dropped; the cell is (torch.bucketize(g_x, x_bins) - 1, torch.bucketize(g_y, y_bins) - 1).
+ * Outputs.  hm [S][2][n][n] float32: hm[s][0][ix][iy] = the largest g_z of the cell (0 where empty), hm[s][1][ix][iy] = 1.0 where something
+ *   fell; every element is written.  point_labels (may be NULL) [n_points][C] int16: the label camera c sees at the point, -1 where it does
+ *   not see it; written for every row some sample owns.  The maximum is an integer atomic on an order-preserving key: two launches on the
+ *   same input are bit-identical.
+ * Launch.  Three launches on the stream: sentinel fill, one thread per item with the sample in the grid's second dimension, finalize.
+ *   max_points: an upper bound of every N_s known on the host (n_points always is one) -- it sizes the grid, the offsets are read on the
+ *   device only.  The entry neither synchronises nor allocates nor reads anything back (capturable).  S <= 65535, S*n*n < 2^31. */
+typedef struct MfTerrainLabelsDesc {
+  int32_t S, C, Hi, Wi;          /* samples, cameras per sample, mask rows and columns */
+  int32_t T, Fx, Fy;             /* poses per sample, footprint points along x and y */
+  int32_t n;                     /* bin edges per axis: the map is n x n */
+  int32_t n_points, max_points;  /* rows of points; upper bound of a sample's rows */
+  int64_t rots_stride_s, trans_stride_s, intrins_stride_s; /* elements between two samples' cameras, or 0: shared */
+  uint32_t class_set[8];         /* 256 bits: the labels that count as rigid */
+  double clearance;              /* |clearance| is taken off the z translation of every pose */
+  float d_max, h_min, h_max;
+  float r_min;                   /* < 0: no inner radius filter */
+  float inv_res;                 /* 1 / grid_res: first guess of the bin (the edges decide) */
+  int32_t reserved;
+} MfTerrainLabelsDesc;
+int mf_terrain_labels_f32(const MfTerrainLabelsDesc* desc, const float* points, const int32_t* offsets, const uint8_t* seg, const float* rots,
+                          const float* trans, const float* intrins, const double* pose_align, const double* poses, const float* fx,
+                          const float* fy, const float* x_bins, const float* y_bins, int32_t* scratch, float* hm, int16_t* point_labels,
+                          void* hip_stream);
+
 /* ---- interpolate_grid (dphysics.py:385-455) on its own: the reference's public sampling method, bug for bug --
  * grid[Bg][H][W] with Bg = B, or one map for all rows (map_shared); xq, yq [B][N] query positions; z_out [B][N];
  * n_out [B][N][3] unit normals (may be NULL: return_normals=False); cells_out [B][N][4] int32 (may be NULL) = the CLAMPED flat

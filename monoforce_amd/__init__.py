@@ -35,4 +35,7 @@ def __getattr__(name):
     if name in ('RoutePlanner', 'cost_to_go', 'extract_route', 'cost_to_go_aten', 'extract_route_host'):
         from . import route
         return getattr(route, name)
+    if name in ('rigid_terrain_heightmap', 'rigid_terrain_heightmap_aten', 'semantic_cloud', 'footprint_traj_points'):
+        from . import labels
+        return getattr(labels, name)
     raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -8,7 +8,7 @@ tensors -> pointers (`c_args`), the current stream last, `check` (one exception,
 acquired on, not the current one).  `size_query` is the same for the two byte-count queries.  WHICH
 arguments an entry point takes is written down once, in the module that owns it: rollout_launch.py (`mf_rollout_*`,
 `mf_reduce_grad_copies_*`), splat.py (`mf_bev_*`), losses.py (`mf_physics_loss_*`, `mf_pose_loss_*`, `mf_nearest_steps_*`, `mf_hm_loss_*`, `mf_total_variation_*`),
-terrain_stage.py, cloudproc.py, fit.py (`mf_terrain_fit_*`), refine.py (`mf_traj_objective_*`, `mf_control_refine_update_*`), dphysics.py (`mf_interpolate_grid_*`), costmap.py (`mf_traversability_*`), route.py (`mf_cost_to_go_*`, `mf_extract_route_*`), ops.py (MPPI and pose costs); tests/test_capi_cpu.py holds
+terrain_stage.py, cloudproc.py, fit.py (`mf_terrain_fit_*`), refine.py (`mf_traj_objective_*`, `mf_control_refine_update_*`), dphysics.py (`mf_interpolate_grid_*`), costmap.py (`mf_traversability_*`), route.py (`mf_cost_to_go_*`, `mf_extract_route_*`), labels.py (`mf_terrain_labels_*`), ops.py (MPPI and pose costs); tests/test_capi_cpu.py holds
 the tree to that.  Importing this module loads nothing: the library comes in at the first `lib()`.
 """
 import contextlib
@@ -143,6 +143,14 @@ class MfTraversabilityDesc(C.Structure):
                 ('lo', C.c_float * 3), ('hi', C.c_float * 3)]
 
 
+class MfTerrainLabelsDesc(C.Structure):
+    _fields_ = [('S', C.c_int32), ('C', C.c_int32), ('Hi', C.c_int32), ('Wi', C.c_int32), ('T', C.c_int32), ('Fx', C.c_int32), ('Fy', C.c_int32),
+                ('n', C.c_int32), ('n_points', C.c_int32), ('max_points', C.c_int32),
+                ('rots_stride_s', C.c_int64), ('trans_stride_s', C.c_int64), ('intrins_stride_s', C.c_int64),
+                ('class_set', C.c_uint32 * 8), ('clearance', C.c_double),
+                ('d_max', C.c_float), ('h_min', C.c_float), ('h_max', C.c_float), ('r_min', C.c_float), ('inv_res', C.c_float), ('reserved', C.c_int32)]
+
+
 MF_ROUTE_TILE, MF_ROUTE_MAX_VERTICES = 32, 256
 MF_ROUTE_GOAL_BLOCKED, MF_ROUTE_NOT_CONVERGED, MF_ROUTE_START_UNREACHABLE, MF_ROUTE_TRUNCATED = 1, 2, 4, 8
 
@@ -162,7 +170,7 @@ class MfRouteDesc(C.Structure):
 SYMBOLS = ['mf_rollout_force_stride', 'mf_rollout_fwd_f32', 'mf_rollout_fwd_f64', 'mf_rollout_default_state_f32', 'mf_rollout_default_state_f64', 'mf_rollout_bwd_f32', 'mf_rollout_bwd_f64', 'mf_rollout_bwd_wants_gcontrols', 'mf_rollout_record_bytes', 'mf_rollout_record_bytes_f64', 'mf_rollout_fwd_stages_zmu', 'mf_rollout_loss_fusable', 'mf_rollout_bwd_window', 'mf_bev_splat_workspace_bytes', 'mf_bev_splat_prepare', 'mf_bev_splat_prepare_cameras', 'mf_bev_splat_prepare_rig',
            'mf_bev_splat_fwd_f32', 'mf_bev_splat_fwd_f64', 'mf_bev_splat_bwd_f32', 'mf_bev_splat_bwd_f64',
            'mf_bev_lift_splat_fwd_f32', 'mf_bev_lift_splat_fwd_f64', 'mf_bev_lift_splat_bwd_f32', 'mf_bev_lift_splat_bwd_f64',
-           'mf_physics_loss_fwd_f32', 'mf_physics_loss_fwd_f64', 'mf_physics_loss_bwd_f32', 'mf_physics_loss_bwd_f64', 'mf_physics_loss_value_f32', 'mf_physics_loss_value_f64', 'mf_nearest_steps_f32', 'mf_nearest_steps_f64', 'mf_reduce_grad_copies_f32', 'mf_reduce_grad_copies_f64', 'mf_estimate_heightmap_f32', 'mf_interpolate_grid_f32', 'mf_interpolate_grid_f64', 'mf_terrain_stage_fwd_f32', 'mf_terrain_stage_bwd_f32', 'mf_mppi_perturb_f32', 'mf_path_costs_f32', 'mf_mppi_scratch_bytes', 'mf_mppi_update_f32', 'mf_pose_costs_f32', 'mf_pose_loss_value_f32', 'mf_pose_loss_value_f64', 'mf_pose_loss_bwd_f32', 'mf_pose_loss_bwd_f64', 'mf_hm_loss_value_f32', 'mf_hm_loss_value_f64', 'mf_hm_loss_bwd_f32', 'mf_hm_loss_bwd_f64', 'mf_total_variation_value_f32', 'mf_total_variation_value_f64', 'mf_total_variation_bwd_f32', 'mf_total_variation_bwd_f64', 'mf_terrain_fit_update_f32', 'mf_terrain_fit_update_f64', 'mf_terrain_fit_grid_cap', 'mf_traj_objective_f32', 'mf_control_refine_update_f32', 'mf_traversability_f32', 'mf_traversability_f64', 'mf_cost_to_go_work_ints', 'mf_cost_to_go_f32', 'mf_cost_to_go_f64', 'mf_extract_route_f32', 'mf_extract_route_f64', 'mf_last_error', 'mf_last_launch', 'mf_version', 'mf_sizeof']
+           'mf_physics_loss_fwd_f32', 'mf_physics_loss_fwd_f64', 'mf_physics_loss_bwd_f32', 'mf_physics_loss_bwd_f64', 'mf_physics_loss_value_f32', 'mf_physics_loss_value_f64', 'mf_nearest_steps_f32', 'mf_nearest_steps_f64', 'mf_reduce_grad_copies_f32', 'mf_reduce_grad_copies_f64', 'mf_estimate_heightmap_f32', 'mf_interpolate_grid_f32', 'mf_interpolate_grid_f64', 'mf_terrain_stage_fwd_f32', 'mf_terrain_stage_bwd_f32', 'mf_mppi_perturb_f32', 'mf_path_costs_f32', 'mf_mppi_scratch_bytes', 'mf_mppi_update_f32', 'mf_pose_costs_f32', 'mf_pose_loss_value_f32', 'mf_pose_loss_value_f64', 'mf_pose_loss_bwd_f32', 'mf_pose_loss_bwd_f64', 'mf_hm_loss_value_f32', 'mf_hm_loss_value_f64', 'mf_hm_loss_bwd_f32', 'mf_hm_loss_bwd_f64', 'mf_total_variation_value_f32', 'mf_total_variation_value_f64', 'mf_total_variation_bwd_f32', 'mf_total_variation_bwd_f64', 'mf_terrain_fit_update_f32', 'mf_terrain_fit_update_f64', 'mf_terrain_fit_grid_cap', 'mf_traj_objective_f32', 'mf_control_refine_update_f32', 'mf_traversability_f32', 'mf_traversability_f64', 'mf_cost_to_go_work_ints', 'mf_cost_to_go_f32', 'mf_cost_to_go_f64', 'mf_extract_route_f32', 'mf_extract_route_f64', 'mf_terrain_labels_f32', 'mf_last_error', 'mf_last_launch', 'mf_version', 'mf_sizeof']
 
 _lib = None
 _lock = threading.Lock()
@@ -186,7 +194,7 @@ def lib():
                 L.mf_last_launch.restype = C.c_char_p
                 for name in SYMBOLS:
                     fn = getattr(L, name)   # AttributeError if the build is stale
-                    if name.startswith(('mf_rollout', 'mf_bev', 'mf_physics', 'mf_estimate', 'mf_terrain_stage', 'mf_terrain_fit', 'mf_reduce', 'mf_interpolate', 'mf_nearest', 'mf_mppi', 'mf_path', 'mf_pose', 'mf_hm_loss', 'mf_total_variation', 'mf_traj', 'mf_control', 'mf_traversability', 'mf_cost_to_go', 'mf_extract_route')):
+                    if name.startswith(('mf_rollout', 'mf_bev', 'mf_physics', 'mf_estimate', 'mf_terrain_stage', 'mf_terrain_fit', 'mf_terrain_labels', 'mf_reduce', 'mf_interpolate', 'mf_nearest', 'mf_mppi', 'mf_path', 'mf_pose', 'mf_hm_loss', 'mf_total_variation', 'mf_traj', 'mf_control', 'mf_traversability', 'mf_cost_to_go', 'mf_extract_route')):
                         fn.restype = C.c_int
                 L.mf_bev_splat_workspace_bytes.restype = C.c_size_t
                 L.mf_rollout_record_bytes.restype = C.c_longlong

@@ -76,6 +76,7 @@ extern "C" int mf_sizeof(const char* name) {
   if (!strcmp(name, "MfTrajObjDesc")) return (int)sizeof(MfTrajObjDesc);
   if (!strcmp(name, "MfRefineDesc")) return (int)sizeof(MfRefineDesc);
   if (!strcmp(name, "MfTraversabilityDesc")) return (int)sizeof(MfTraversabilityDesc);
+  if (!strcmp(name, "MfTerrainLabelsDesc")) return (int)sizeof(MfTerrainLabelsDesc);
   if (!strcmp(name, "MfCostToGoDesc")) return (int)sizeof(MfCostToGoDesc);
   if (!strcmp(name, "MfRouteDesc")) return (int)sizeof(MfRouteDesc);
   return -1;
